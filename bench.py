@@ -46,6 +46,24 @@ def b_alg(V, O, P, n):
     return 24 * V + 32 * O + 16 * P + 24 * n
 
 
+DUMP_MAX_BODIES = 1 << 20  # x 36 B per body (pos, vel, acc in fp32) = 38 MB, within the 64 MB a dump may take
+
+
+def dump_outputs(path, pos, vel, acc):
+    """--dump-outputs: what the timed path computed in its last step, in caller (upload) order: positions and
+    velocities after the step and the accelerations of its force pass, float32 [n, 3] each, as pos.npy, vel.npy,
+    acc.npy.  Above DUMP_MAX_BODIES bodies, the rows of a fixed seeded sample of body indices (ascending), the same
+    sample for every run with the same body count."""
+    import numpy as np
+    n = len(pos)
+    if n > DUMP_MAX_BODIES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BODIES, replace=False))
+        pos, vel, acc = pos[rows], vel[rows], acc[rows]
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("pos", pos), ("vel", vel), ("acc", acc)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def csrc_sha16():
     """identity of the kernels this run executes: sha256 over the library's sources (the GPU box has no .git)"""
     import hashlib
@@ -290,7 +308,13 @@ def main():
                          "the force-launch time of the roofline block then comes from 10 extra timed-stage steps)")
     ap.add_argument("--force-variant", type=int, default=0,
                     help="A/B: 0 = hand-scheduled force walk (default), 1 = compiler-scheduled walk")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state and accelerations of the last timed step as "
+                         "DIR/pos.npy, vel.npy, acc.npy (float32 [n, 3], caller order; a fixed seeded sample of "
+                         f"{DUMP_MAX_BODIES:,} bodies above that many)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_baseline_child:
         return cpu_baseline_child(args.n, args.theta, args.seed, args.child_budget, args.child_steps)
     # stdout carries exactly ONE line, the JSON: libraries that print banners to fd 1 (RCCL prints its version
@@ -477,6 +501,26 @@ def main():
             stepper.step(args.steps)
     barrier()
     elapsed = reduce_max(time.perf_counter() - t0)
+
+    # read back before any further step (stage timings, profiling, strong scaling) moves the state on
+    if args.dump_outputs:
+        if dist_mode == "domain":   # every rank holds its own bodies: gathered to rank 0 and placed by body id
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(stepper.local_state(), parts, dst=0)
+            if rank == 0:
+                pos, vel, acc = [np.zeros((n_total, 3), np.float32) for _ in range(3)]
+                seen = np.zeros(n_total, np.int32)
+                for ids, posm, v, a in parts:
+                    pos[ids], vel[ids], acc[ids] = posm[:, :3], v, a
+                    seen[ids] += 1
+                assert (seen == 1).all(), "every body must be owned by exactly one rank"
+                dump_outputs(args.dump_outputs, pos, vel, acc)
+            del parts
+        elif rank == 0:             # one engine, or a replicated one: rank 0 holds every body
+            x, y, z, vx, vy, vz = eng.download()
+            dump_outputs(args.dump_outputs, np.stack([x, y, z], 1), np.stack([vx, vy, vz], 1),
+                         np.stack(eng.download_acc(), 1))
+        barrier()
 
     # per-phase device times of the domain-decomposed step: 5 further steps on every rank (the exchanges are
     # collective), events on rank 0's stream only — NOT in the timed region: each event record costs the stream

@@ -24,15 +24,16 @@ def _free_port():
 
 
 @pytest.mark.parametrize("mode,word", [("domain", "domain decomposition"), ("replicated", "sharded")])
-def test_bench_distributed_path_world1(mode, word):
+def test_bench_distributed_path_world1(mode, word, tmp_path):
     env = dict(os.environ)
     env["BH_FORCE_DIST"] = "1"
     env["BH_DIST_MODE"] = mode
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    d = tmp_path / "dump"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--bodies", "200000", "--no-cpu-baseline"]
+           "--bodies", "200000", "--no-cpu-baseline", "--dump-outputs", str(d)]
     r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -50,21 +51,55 @@ def test_bench_distributed_path_world1(mode, word):
         assert "library RCCL transport" in out["config"]["parallelism"]      # ncclCommInitRank at world size 1
         assert out["strong"]["n_total"] == 200000 and out["strong"]["value"] > 0 and out["strong"]["scaling"] == "strong"
         assert out["config"]["domain"]["phase_ms_rank0"]["top_remote_force"] > 0
+    # the dump of the NCCL-backed path (domain: the rank's bodies gathered through torch.distributed)
+    for k in ("pos", "vel", "acc"):
+        a = np.load(d / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == (200000, 3) and np.isfinite(a).all()
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(pkg, tmp_path):
+    """--dump-outputs writes the state and accelerations after exactly warmup + steps whole steps, in caller order:
+    the same bits as an Engine stepped that often from the same input (bh_step is reproducible bit for bit), and
+    not those of one step fewer"""
+    n, warmup, steps = 65536, 2, 3
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--bodies", str(n), "--no-cpu-baseline", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, cwd=ROOT, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    out = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    got = {k: np.load(d / f"{k}.npy") for k in ("pos", "vel", "acc")}
+    assert sorted(os.listdir(d)) == ["acc.npy", "pos.npy", "vel.npy"]
+    for a in got.values():
+        assert a.dtype == np.float32 and a.shape == (n, 3) and np.isfinite(a).all()
+    with pkg.Engine(n) as e:
+        e.upload(*pkg.plummer(n, seed=42))
+        e.step(warmup + steps - 1)
+        before = np.stack(e.download()[:3], 1)
+        e.step(1)
+        x, y, z, vx, vy, vz = e.download()
+        ref = {"pos": np.stack([x, y, z], 1), "vel": np.stack([vx, vy, vz], 1), "acc": np.stack(e.download_acc(), 1)}
+    for k in ref:
+        assert np.array_equal(got[k], ref[k]), f"{k}: max |diff| {np.abs(got[k] - ref[k]).max()}"
+    assert not np.array_equal(got["pos"], before)
 
 
 @pytest.mark.parametrize("mode", ["domain", "replicated"])
-def test_bench_two_ranks_rehearsal(mode):
+def test_bench_two_ranks_rehearsal(mode, pkg, tmp_path):
     """bench.py end to end with WORLD_SIZE=2 (both ranks on this one GPU, gloo instead of RCCL): the
     N > 1 code path of the benchmark itself — IC generation for 2 x bodies, stepper, timing reduction,
-    JSON assembly.  The throughput of such a run is meaningless and not checked."""
+    JSON assembly, the dump of every rank's bodies in caller order.  The throughput of such a run is
+    meaningless and not checked."""
     env = dict(os.environ)
     env["BH_BENCH_REHEARSAL"] = "1"
     env["BH_DIST_MODE"] = mode
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    d = tmp_path / "dump"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--bodies", "150000", "--no-cpu-baseline"]
+           "--bodies", "150000", "--no-cpu-baseline", "--dump-outputs", str(d)]
     r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -79,6 +114,16 @@ def test_bench_two_ranks_rehearsal(mode):
         dom = out["config"]["domain"]
         assert dom["force_passes"].startswith("adaptive") and dom["split_now_rank0"] in (0, 1)
         assert "x4_ms_measured_rank0" in dom   # (null here: 150,000 bodies per rank never split)
+    # the dump: all 300,000 bodies after the 5 steps, each where a single context stepped 5 times puts it (the
+    # tolerances of tests/dd_gpu_worker.py: the walk forms of the ranks' launches differ from bh_step's)
+    pos, acc = np.load(d / "pos.npy"), np.load(d / "acc.npy")
+    assert pos.shape == acc.shape == np.load(d / "vel.npy").shape == (300000, 3) and pos.dtype == np.float32
+    with pkg.Engine(300000) as e:
+        e.upload(*pkg.plummer(300000, seed=42))
+        e.step(5)
+        p1, a1 = np.stack(e.download()[:3], 1), np.stack(e.download_acc(), 1)
+    rel = np.linalg.norm(acc - a1, axis=1) / np.maximum(np.linalg.norm(a1, axis=1), 1e-30)
+    assert np.abs(pos - p1).max() < 5e-2 and np.median(rel) < 1e-4
 
 
 def test_bench_two_ranks_domain_fallback_is_collective():
