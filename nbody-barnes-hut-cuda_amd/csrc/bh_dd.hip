@@ -2333,7 +2333,7 @@ static int dd_force_local_launch(bh_ctx* c, bool after_let) {
     BH_HIP(c, hipEventRecord(d->ev_let, c->stream));
     BH_HIP(c, hipStreamWaitEvent(so, d->ev_let, 0));
   }
-  if (d->own_hi > 0) BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base2, so, c->acc));
+  if (d->own_hi > 0) BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base2, so, c->acc, &c->info->dd_hold));
   BH_HIP(c, hipEventRecord(d->ev_own, so));
   return BH_OK;
 }
@@ -2439,9 +2439,10 @@ static int dd_force_impl(bh_ctx* c, bool allow_fuse) {
     BH_HIP(c, hipEventRecord(d->ev_x4, c->stream));  // X4, the validation and both top trees are complete here
     BH_HIP(c, hipStreamWaitEvent(so, d->ev_x4, 0));
     if (d->own_hi > 0)
-      BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base, so, d->acc2, c->acc, allow_fuse, &f1, groups));
+      BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base, so, d->acc2, &c->info->dd_hold, c->acc, allow_fuse, &f1,
+                               groups));
     BH_HIP(c, hipEventRecord(d->ev_own, so));
-    BH_HIP(c, bhk_force_root(c, d->own_hi, c->n, d->top_base3, c->stream, c->acc, nullptr,
+    BH_HIP(c, bhk_force_root(c, d->own_hi, c->n, d->top_base3, c->stream, c->acc, &c->info->dd_hold, nullptr,
                              allow_fuse && (f1 || d->own_hi == 0), &f2, groups));
     BH_HIP(c, hipStreamWaitEvent(c->stream, d->ev_own, 0));
     // (both launches take the fused instance or neither: the same conditions decide — a mixed outcome would leave
@@ -2451,10 +2452,12 @@ static int dd_force_impl(bh_ctx* c, bool allow_fuse) {
     c->acc2 = d->acc2;
   } else if (d->split) {  // remote pass -> acc2; acc + acc2 is integrated once the own pass has finished too
     BH_HIP(c, hipStreamWaitEvent(c->stream, d->ev_own, 0));
-    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, d->acc2, c->acc, allow_fuse, &fused));
+    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, d->acc2, &c->info->dd_hold, c->acc, allow_fuse,
+                             &fused));
     c->acc2 = d->acc2;
   } else {
-    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, c->acc, nullptr, allow_fuse, &fused));
+    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, c->acc, &c->info->dd_hold, nullptr, allow_fuse,
+                             &fused));
     c->acc2 = nullptr;
   }
   c->dd_integrated = fused;
@@ -2646,11 +2649,11 @@ int bh_dd_pass_times(bh_ctx* c, float ms[4]) {
   ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
   for (int rep = 0; rep < 2; rep++) {
     BH_HIP(c, hipEventRecord(e[0], c->stream));
-    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base2, c->stream, c->acc));
+    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base2, c->stream, c->acc, &c->info->dd_hold));
     BH_HIP(c, hipEventRecord(e[1], c->stream));
-    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base, c->stream, d->acc2));
+    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base, c->stream, d->acc2, &c->info->dd_hold));
     BH_HIP(c, hipEventRecord(e[2], c->stream));
-    if (partial) BH_HIP(c, bhk_force_root(c, oh, c->n, d->top_base3, c->stream, c->acc));
+    if (partial) BH_HIP(c, bhk_force_root(c, oh, c->n, d->top_base3, c->stream, c->acc, &c->info->dd_hold));
     BH_HIP(c, hipEventRecord(e[3], c->stream));
     BH_HIP(c, hipStreamSynchronize(c->stream));
   }
@@ -2661,13 +2664,13 @@ int bh_dd_pass_times(bh_ctx* c, float ms[4]) {
   BH_HIP(c, hipEventRecord(e[0], c->stream));
   BH_HIP(c, hipStreamWaitEvent(d->stream_own, e[0], 0));
   if (partial) {
-    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base, d->stream_own, d->acc2));
+    if (oh > 0) BH_HIP(c, bhk_force_root(c, 0, oh, d->top_base, d->stream_own, d->acc2, &c->info->dd_hold));
     BH_HIP(c, hipEventRecord(e[4], d->stream_own));
-    BH_HIP(c, bhk_force_root(c, oh, c->n, d->top_base3, c->stream, c->acc));
+    BH_HIP(c, bhk_force_root(c, oh, c->n, d->top_base3, c->stream, c->acc, &c->info->dd_hold));
   } else {
-    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base2, d->stream_own, c->acc));
+    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base2, d->stream_own, c->acc, &c->info->dd_hold));
     BH_HIP(c, hipEventRecord(e[4], d->stream_own));
-    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, d->acc2));
+    BH_HIP(c, bhk_force_root(c, 0, c->n, d->top_base, c->stream, d->acc2, &c->info->dd_hold));
   }
   BH_HIP(c, hipStreamWaitEvent(c->stream, e[4], 0));
   BH_HIP(c, hipEventRecord(e[1], c->stream));

@@ -1024,16 +1024,20 @@ __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_fast_kernel(const flo
 // Per block the same code as the depth-first walk (BH_WALK_BODY); a push is 4 v_mov + ds_write_b96 instead of
 // 3 v_writelane, a pop ds_read_b96 + 3 v_readfirstlane instead of 3 v_readlane.
 // LDS per workgroup: 2 levels x K lists x kCoopSub bytes: [count, -, -, -][kCoopCap entries of 16 bytes].
-// (list size = 1 << SUBSH bytes, SUBSH 11 / 12 / 13: 127 / 255 / 511 entries per wave and level; the product uses 11 — the entries of a
-// level grow like theta^-3, see force_coop_subsh; an entry a full list cannot take is walked depth-first by its wave)
+// Level-list size (1 << kCoopSubsh bytes per wave and level): 127 entries.  The entries of a level are the cells the
+// group's bodies open on it — the longest list any wave writes grows like theta^-3 and hardly with the body count
+// (K = 4, 1M Plummer: 76 at theta 0.5, 105 at 0.4, 170 at 0.3, 334 at 0.2; profiles/r04_coop/lists.txt); what a full
+// list does not take goes onto the wave's own stack (BH_PUSH1) and is walked depth-first.  Larger lists cost the mixed
+// launch its occupancy (LDS is allocated per workgroup for the one-wave groups too: 35 KB instead of 19.5 -> 4 waves
+// per SIMD).
 constexpr int kCoopMaxK = 8;
-__host__ __device__ constexpr int coop_sub(int subsh) { return 1 << subsh; }
-__host__ __device__ constexpr int coop_cap(int subsh) { return (1 << subsh) / 16 - 1; }
+constexpr int kCoopSubsh = 11;
+constexpr int kCoopSub = 1 << kCoopSubsh;
+constexpr int kCoopCap = kCoopSub / 16 - 1;
 
 // One wave's share of the cooperative walk.  cur / nxt: LDS byte addresses of the two level buffers (cur holds the
 // root entry in list 0, every other count is zero; the caller has synchronised).  Returns false when a list
 // overflowed or a block of more than 8 children was met (ax..az are then partial sums of an incomplete walk).
-template <int SUBSH>
 __device__ __forceinline__ bool coop_traverse_asm(const float* frec, u32 cur, u32 nxt, int K, int j, float px,
                                                   float py, float pz, float eps2, float& ax, float& ay, float& az,
                                                   bool& limit_hit) {
@@ -1148,8 +1152,8 @@ __device__ __forceinline__ bool coop_traverse_asm(const float* frec, u32 cur, u3
       "s_mov_b32 %[maxc], s16\n"
       : [ax] "=&v"(ax), [ay] "=&v"(ay), [az] "=&v"(az), [maxc] "=s"(maxc)
       : [base] "s"(frec), [cur] "s"(cur), [nxt] "s"(nxt), [K] "s"(K), [j] "s"(j), [px] "v"(px), [py] "v"(py),
-        [pz] "v"(pz), [eps2] "s"(eps2), [sub] "n"(coop_sub(SUBSH)), [subsh] "n"(SUBSH), [capb] "n"(coop_cap(SUBSH) * 16),
-        [cap] "n"(coop_cap(SUBSH)),
+        [pz] "v"(pz), [eps2] "s"(eps2), [sub] "n"(kCoopSub), [subsh] "n"(kCoopSubsh), [capb] "n"(kCoopCap * 16),
+        [cap] "n"(kCoopCap),
         [use_budget] "n"(0), [stats] "n"(0), [pf] "n"(0), [coop] "n"(1)
       : "memory", "vcc", "scc", "m0",
         "s10", "s11", "s12", "s13", "s14", "s15", "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24",
@@ -1170,10 +1174,10 @@ __device__ __forceinline__ bool coop_traverse_asm(const float* frec, u32 cur, u3
 // (fuse_integrate_and_fold; g = the group's index in the launch).  A group whose walk overflowed a level list (or holds
 // an unsplit cell of more than 8 bodies) is redone by wave 0 with the generic depth-first loop: the same decision on
 // every run, so still reproducible.
-__host__ __device__ constexpr size_t coop_lds_bytes(int K, int subsh) {
-  return (size_t)K * (2 * coop_sub(subsh) + 64 * 3 * sizeof(float) + sizeof(u32));
+__host__ __device__ constexpr size_t coop_lds_bytes(int K) {
+  return (size_t)K * (2 * kCoopSub + 64 * 3 * sizeof(float) + sizeof(u32));
 }
-template <bool FUSE, int SUBSH, bool TRACE = false>
+template <bool FUSE, bool TRACE = false>
 __device__ __forceinline__ void coop_group(u32* coop_lds, int K, int j, int lane, const float* __restrict__ frec_g,
                                            const float4* posm, float4* __restrict__ acc, int lo, int hi, float eps2,
                                            bh_devinfo* __restrict__ info, int g, int group, const bh_fuse_args& fz,
@@ -1190,7 +1194,6 @@ __device__ __forceinline__ void coop_group(u32* coop_lds, int K, int j, int lane
   const u64 m0 = __builtin_amdgcn_ballot_w64(valid);
   if (m0 == 0) return;  // the whole workgroup: every wave holds the same bodies
   // level buffers: [2][K][kCoopSub bytes]; then the partial accelerations [K][64][3] and K flags
-  constexpr int kCoopSub = coop_sub(SUBSH);
   u32* const lvl = coop_lds;
   float* const part = reinterpret_cast<float*>(coop_lds + 2 * K * (kCoopSub / 4));
   u32* const bad = coop_lds + 2 * K * (kCoopSub / 4) + K * 192;
@@ -1206,7 +1209,7 @@ __device__ __forceinline__ void coop_group(u32* coop_lds, int K, int j, int lane
   const u32 cur = (u32)(size_t)(__attribute__((address_space(3))) u32*)lvl;
   float ax, ay, az;
   bool lim = false;
-  const bool ok = coop_traverse_asm<SUBSH>(frec_g, cur, cur + (u32)K * kCoopSub, K, j, px, py, pz, eps2, ax, ay, az,
+  const bool ok = coop_traverse_asm(frec_g, cur, cur + (u32)K * kCoopSub, K, j, px, py, pz, eps2, ax, ay, az,
                                            lim);
   if (TRACE && lane == 0) trace_row(fz.trace, trace_row0 + j, tr0);
   part[(j * 64 + lane) * 3 + 0] = ax;
@@ -1241,7 +1244,7 @@ __device__ __forceinline__ void coop_group(u32* coop_lds, int K, int j, int lane
 }
 
 // every group of the launch by K = blockDim.x / 64 waves (2..8): launches that would not fill the GPU otherwise
-template <bool FUSE, int SUBSH, bool TRACE = false>
+template <bool FUSE, bool TRACE = false>
 __global__ __launch_bounds__(512) BH_WALK_SGPRS void force_coop_kernel(const float* __restrict__ frec_g, const float4* posm,
                                                          float4* __restrict__ acc, int lo, int hi, float eps2,
                                                          int xcd_mode, bh_devinfo* __restrict__ info, int group,
@@ -1253,7 +1256,7 @@ __global__ __launch_bounds__(512) BH_WALK_SGPRS void force_coop_kernel(const flo
   const int g = block_chunk(xcd_mode);  // one group per workgroup
   // (lo is a multiple of the group size: lo / group + g is the group's index among all groups of the context — what
   // the fused epilogue files its rows under when several launches share one fold, bhk_force_root)
-  coop_group<FUSE, SUBSH, TRACE>(coop_lds, K, rfl((int)(threadIdx.x >> 6)), threadIdx.x & 63, frec_g, posm, acc, 0, hi,
+  coop_group<FUSE, TRACE>(coop_lds, K, rfl((int)(threadIdx.x >> 6)), threadIdx.x & 63, frec_g, posm, acc, 0, hi,
                                  eps2, info, lo / group + g, group, fz, g * K, root, held);
 }
 
@@ -1272,14 +1275,14 @@ constexpr int kMixedRun = 16;  // chunks (workgroups of four groups) per XCD run
 #define BH_TAIL_RUN 16
 #endif
 constexpr int kTailRun = BH_TAIL_RUN;  // groups of the cooperative tail per XCD run
-template <bool FUSE, int SUBSH, bool BUDGET = false, bool TRACE = false>
+template <bool FUSE, bool BUDGET = false, bool TRACE = false>
 __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_mixed_kernel(const float* __restrict__ frec_g, const float4* posm,
                                                           float4* __restrict__ acc, int hi, float eps2, int xcd_mode,
                                                           bh_devinfo* __restrict__ info, int nbulk, int gb,
                                                           bh_fuse_args fz, int root = 0, int g0 = 0,
                                                           const int* __restrict__ hold = nullptr) {
   // g0: the launch covers the groups g0 .. of the context (bodies [64 g0, hi)), gb of them by one wave each
-  __shared__ __attribute__((aligned(16))) u32 coop_lds[coop_lds_bytes(kMixedK, SUBSH) / 4];
+  __shared__ __attribute__((aligned(16))) u32 coop_lds[coop_lds_bytes(kMixedK) / 4];
   const int held = force_hold_load(hold);
   const int lane = threadIdx.x & 63;
   const int wib = rfl((int)(threadIdx.x >> 6));
@@ -1287,7 +1290,7 @@ __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_mixed_kernel(const fl
     // (XCD placement of the tail as of the bulk: runs of kTailRun consecutive groups per XCD; nbulk is a multiple of
     // eight in mode 2, so a workgroup's XCD is also that of its index in the tail)
     const int t = block_chunk_of<kTailRun>(xcd_mode == 2 ? 2 : 1, (int)blockIdx.x - nbulk, 0);
-    coop_group<FUSE, SUBSH, TRACE>(coop_lds, kMixedK, wib, lane, frec_g, posm, acc, 0, hi, eps2, info, g0 + gb + t, 64,
+    coop_group<FUSE, TRACE>(coop_lds, kMixedK, wib, lane, frec_g, posm, acc, 0, hi, eps2, info, g0 + gb + t, 64,
                                    fz, gb + t * kMixedK, root, held);
     return;
   }
@@ -1443,6 +1446,16 @@ __global__ __launch_bounds__(256) void unpack_u32x3_kernel(const u32* __restrict
 
 }  // namespace
 
+// Design-study builds (tools/mkvariant.sh study -DBH_STUDY) take a few knobs from the environment; product builds none.
+static const char* study_env(const char* name) {
+#ifdef BH_STUDY
+  return getenv(name);
+#else
+  (void)name;
+  return nullptr;
+#endif
+}
+
 // bodies per wave of the fast walk: fewer than 64 (upper lanes idle) when 64 would leave the 1024 SIMDs with one
 // or two waves each — smaller groups walk smaller unions of records and more waves hide each other's scalar-load
 // latency.  Measured force ms with the four-line prefetch (16 / 32 / 64 bodies per wave): 8,192 bodies 0.150 /
@@ -1455,79 +1468,227 @@ static int force_group(const bh_ctx* c, int bodies) {
   return bodies <= 20 * 1024 ? 16 : (bodies <= 56 * 1024 ? 32 : 64);
 }
 
+// threads per workgroup of the one-wave walk: bh_params.force_block 64, 128 or 256 (else the default)
+static int force_block(const bh_ctx* c) {
+  const int tpb = c->p.force_block;
+  return tpb == 64 || tpb == 128 || tpb == 256 ? tpb : BH_FORCE_BLOCK_DEFAULT;
+}
+
 constexpr int kWalkWaves = 8;  // resident waves per SIMD of the walk kernels (BH_WALK_SGPRS: 80 scalar registers)
 constexpr int kTailWaves = 7;  // ... the cooperative tail of a mixed launch is sized with (round 4's figure; with eight
                                // the fused 1M launch measures 1.2 % slower, 500k and 2M alike: profiles/r05_experiments/)
-// Groups at the end of a launch that are walked by four waves each (force_mixed_kernel; a launch of fewer groups is
-// cooperative throughout): the short jobs have to refill what the long ones free while they drain — a third of the
-// resident waves' worth of groups, whatever the launch size (same-box sweep at 1M bodies, force ms for 0 / 2,048 /
-// 2,560 / 3,072 / 3,584 / 4,096 / 5,120 such groups: 1.166 / 1.091 / 1.091 / 1.099 / 1.097 / 1.110 / 1.114;
-// 500,000 bodies: 0.692 / 0.601 / - / 0.604 / - / 0.605; 2M: 2.252 / 2.187 / - / 2.177 / - / 2.178; theta 0.3 at 1M:
-// 3.533 / 3.245 / - / 3.220 / - / 3.232 — profiles/r04_drain/).
-static long long force_tail_groups(const bh_ctx* c) {
-  long long T = (long long)c->num_cus * 4 * kTailWaves / 3;
-#ifdef BH_STUDY
-  static const int env_tail = getenv("BH_FORCE_TAIL") ? atoi(getenv("BH_FORCE_TAIL")) : -1;
-  if (env_tail >= 0) T = env_tail;
-#endif
-  return T;
-}
 
-// Waves per group (bh_params.force_coop: 0 = by context size, 1 = one wave per group: the depth-first walk, 2..8).
-// Decided from the CONTEXT's body count, never from the range of one launch, so that a slab launch of a sharded step
-// (bh_force_range) gives every body the bits of the full launch.  Automatic: as many waves per 64-body group as keep
-// the launch within the ~6 waves per SIMD the walk saturates at.
-static int force_coop(const bh_ctx* c, int group) {
-  if (c->dd || c->p.force_variant != 0) return 1;
-  if (c->p.force_coop >= 1 && c->p.force_coop <= kCoopMaxK) return c->p.force_coop;
-  const long long groups = ((long long)c->n + group - 1) / group;
-  // up to twice the tail of a mixed launch everything is walked cooperatively (same-box, force ms mixed / all by four
-  // waves: 160,000 bodies 0.260 / 0.226, 200,000 0.303 / 0.280, 300,000 0.396 / 0.391; 500,000: 0.603 / 0.627)
-  if (groups > 2 * force_tail_groups(c)) return 1;  // mixed launch: one wave per group first, the last groups by four
-  // eight waves while eight per group still fit the GPU at once (16,384 bodies: 0.048 ms against 0.064 with four;
-  // 32,768: 0.063 / 0.075), else four — one per SIMD of a CU; five to seven measure worse than either (65,536 bodies,
-  // K = 4 / 5 / 6 / 7 / 8: 0.108 / 0.106 / 0.108 / 0.139 / 0.119)
+// Waves per group of a cooperative launch of `groups` groups (bh_params.force_coop 2..8, else automatic): eight while
+// eight per group still fit the GPU at once (16,384 bodies: 0.048 ms against 0.064 with four; 32,768: 0.063 / 0.075),
+// else four — one per SIMD of a CU; five to seven measure worse than either (65,536 bodies, K = 4 / 5 / 6 / 7 / 8:
+// 0.108 / 0.106 / 0.108 / 0.139 / 0.119)
+static int coop_waves(const bh_ctx* c, long long groups) {
+  if (c->p.force_coop >= 2 && c->p.force_coop <= kCoopMaxK) return c->p.force_coop;
   return groups * kCoopMaxK <= (long long)c->num_cus * 4 * kWalkWaves ? kCoopMaxK : 4;
 }
 
-// Level-list size of the cooperative walk (1 << subsh bytes per wave and level): 127 entries.  The entries of a level
-// are the cells the group's bodies open on it — the longest list any wave writes grows like theta^-3 and hardly with
-// the body count (K = 4, 1M Plummer: 76 at theta 0.5, 105 at 0.4, 170 at 0.3, 334 at 0.2; profiles/r04_coop/lists.txt);
-// what a full list does not take goes onto the wave's own stack (BH_PUSH1).  Larger lists cost the mixed launch its
-// occupancy (LDS is allocated per workgroup for the one-wave groups too: 35 KB instead of 19.5 -> 4 waves per SIMD).
-static int force_coop_subsh(const bh_ctx* c) {
-#ifdef BH_STUDY
-  static const int env = getenv("BH_COOP_SUBSH") ? atoi(getenv("BH_COOP_SUBSH")) : 0;
-  if (env >= 11 && env <= 13) return env;
-#endif
-  (void)c;
-  return 11;
+// Waves per group of a single context (bh_params.force_coop: 0 = by context size, 1 = one wave per group: the
+// depth-first walk, 2..8).  Decided from the CONTEXT's body count, never from the range of one launch, so that a slab
+// launch of a sharded step (bh_force_range) gives every body the bits of the full launch.  Automatic: as many waves per
+// 64-body group as keep the launch within the ~6 waves per SIMD the walk saturates at.  T: plan_force.
+static int force_coop(const bh_ctx* c, int group, long long T) {
+  if (c->dd || c->p.force_variant != 0 || c->p.force_coop == 1) return 1;
+  const long long groups = ((long long)c->n + group - 1) / group;
+  // up to twice the tail of a mixed launch everything is walked cooperatively (same-box, force ms mixed / all by four
+  // waves: 160,000 bodies 0.260 / 0.226, 200,000 0.303 / 0.280, 300,000 0.396 / 0.391; 500,000: 0.603 / 0.627)
+  if (c->p.force_coop == 0 && groups > 2 * T) return 1;  // mixed launch: one wave per group first, the last by four
+  return coop_waves(c, groups);
 }
 
+// one-wave groups at the head of a mixed launch of G 64-body groups: whole workgroups of four, T groups left for the tail
+static int mixed_bulk_groups(long long G, long long T) { return (int)((G - T > 0 ? G - T : 0) & ~3ll); }
+
 // Mixed launches (force_mixed_kernel): the bodies below this bound are walked one wave per 64-body group, the rest
-// (force_tail_groups) four waves per group.
+// (T groups) four waves per group.
 // 0: every group cooperatively (K > 1: the launch does not fill the GPU); n: none (force_coop = 1, other walks).
-static int force_bulk_bodies(const bh_ctx* c, int group, int K) {
+static int force_bulk_bodies(const bh_ctx* c, int group, int K, long long T) {
   if (K > 1) return 0;
-  if (c->dd || c->p.force_variant != 0 || c->p.force_coop != 0 || group != 64) return c->n;
-  const long long T = force_tail_groups(c);
-  const long long G = ((long long)c->n + 63) / 64;
-  const long long gb = (G - T > 0 ? G - T : 0) & ~3ll;  // whole workgroups of four one-wave groups
-  return T == 0 ? c->n : (int)(gb * 64);
+  if (c->dd || c->p.force_variant != 0 || c->p.force_coop != 0 || group != 64 || T == 0) return c->n;
+  return mixed_bulk_groups(((long long)c->n + 63) / 64, T) * 64;
 }
 
 // bh_params.xcd_mode 3 (default): interleaved runs when the launch has more waves than the GPU holds at once
 // (8 waves per SIMD: 54 VGPRs), contiguous eighths otherwise
 static int resolve_xcd_mode(const bh_ctx* c, int bodies, int group) {
-  const int mode = c->p.xcd_mode;
-  if (mode != 3) return mode;
-  const long long waves = ((long long)bodies + group - 1) / group;
-  return waves > (long long)c->num_cus * 32 ? 2 : 0;
+  if (c->p.xcd_mode != 3) return c->p.xcd_mode;
+  return ((long long)bodies + group - 1) / group > (long long)c->num_cus * 32 ? 2 : 0;  // waves of the launch
 }
 
-// workgroups of the cooperative tail of a mixed launch: whole XCD runs in mode 2 (the surplus groups hold no body)
-static int mixed_tail_grid(int mmode, int tail) {
-  return mmode == 2 ? (tail + 8 * kTailRun - 1) / (8 * kTailRun) * (8 * kTailRun) : tail;
+// workgroups for `wgs` of them in XCD mode 2: whole runs of `run` per XCD (block_chunk_of; the surplus holds no body)
+static int xcd_grid(int mode, int run, int wgs) {
+  return mode == 2 ? (wgs + 8 * run - 1) / (8 * run) * (8 * run) : wgs;
+}
+
+// One force launch, completely: walk, bodies, groups, grid (plan_force decides it, force_launch makes it).
+//   literal: force_literal_kernel; strict / generic: force_kernel (source-text / fast arithmetic on the canonical
+//   records); fast / fast_pf / fast_v1: force_fast_kernel, one wave per group (hand-scheduled walk without / with the
+//   scalar-cache prefetch, compiler-scheduled walk); coop: force_coop_kernel; mixed: force_mixed_kernel
+enum class force_walk { none, literal, strict, generic, fast, fast_pf, fast_v1, coop, mixed };
+enum class force_entry { single, counting, pass };  // bh_step / bh_force_range; bh_force_count; a decomposed pass
+struct force_plan {
+  force_walk walk = force_walk::none;
+  bool count = false;   // strict / generic: the V / O / P counters
+  bool budget = false;  // the BUDGET instances (decomposed pass)
+  int lo = 0, hi = 0;   // bodies of the launch
+  int group = 0, K = 1; // bodies per group, waves per group (mixed: of the tail)
+  int bulk = 0;         // single context: bodies [0, bulk) one wave per 64-body group, [bulk, n) K waves per group
+  int gb = 0, nbulk = 0, tail = 0;  // mixed: one-wave groups, their workgroups, groups of the cooperative tail
+  int xcd = 0, grid = 0, block = 0;
+  size_t lds = 0;       // dynamic LDS per workgroup
+  int groups() const { return (hi - lo + group - 1) / group; }
+  int rows() const { return walk == force_walk::mixed ? gb + K * tail : groups() * K; }  // waves (trace rows)
+  bool hand() const {  // the hand-scheduled walks, the only ones with FUSE and TRACE instances
+    return walk == force_walk::fast || walk == force_walk::fast_pf || walk == force_walk::coop || walk == force_walk::mixed;
+  }
+};
+
+static force_plan plan_one_wave(const bh_ctx* c, force_plan p, int lo, int hi, int xcd) {
+  p.walk = c->p.force_variant == 1 ? force_walk::fast_v1
+                                   : (hi - lo <= kPrefetchMaxBodies ? force_walk::fast_pf : force_walk::fast);
+  p.lo = lo; p.hi = hi; p.K = 1; p.xcd = xcd;
+  p.block = force_block(c);
+  p.grid = xcd_grid(xcd, kXcdRun, (p.groups() * 64 + p.block - 1) / p.block);
+  return p;
+}
+static force_plan plan_coop(const bh_ctx* c, force_plan p, int lo, int group, int K) {  // a workgroup per group
+  p.walk = force_walk::coop;
+  p.lo = lo; p.group = group; p.K = K;
+  p.xcd = resolve_xcd_mode(c, p.hi - lo, p.group);
+  p.grid = xcd_grid(p.xcd, kXcdRun, p.groups());
+  p.block = K * 64;
+  p.lds = coop_lds_bytes(K);
+  return p;
+}
+// big jobs first, short jobs last: G 64-body groups, the first gb by one wave each
+static force_plan plan_mixed(const bh_ctx* c, force_plan p, int gb, long long G) {
+  p.walk = force_walk::mixed;
+  p.group = 64; p.K = kMixedK; p.gb = gb; p.tail = (int)(G - gb);
+  p.xcd = resolve_xcd_mode(c, gb * 64, 64);
+  p.nbulk = xcd_grid(p.xcd, kMixedRun, gb / 4);
+  p.grid = p.nbulk + xcd_grid(p.xcd, kTailRun, p.tail);
+  p.block = 256;
+  return p;
+}
+
+// The launch of bodies [lo, hi) for entry e.  A single-context range that straddles `bulk` (bh_force_range) is two
+// launches: the returned cooperative part [bulk, hi) and *rest, the one-wave remainder [lo, bulk) (none otherwise).
+static force_plan plan_force(const bh_ctx* c, int lo, int hi, force_entry e, force_plan* rest = nullptr) {
+  force_plan p;
+  if (rest) *rest = p;
+  p.lo = lo; p.hi = hi;
+  if (hi <= lo) return p;
+  // Groups at the end of a launch that are walked by four waves each (force_mixed_kernel; a launch of fewer groups is
+  // cooperative throughout): the short jobs have to refill what the long ones free while they drain — a third of the
+  // resident waves' worth of groups, whatever the launch size (same-box sweep at 1M bodies, force ms for 0 / 2,048 /
+  // 2,560 / 3,072 / 3,584 / 4,096 / 5,120 such groups: 1.166 / 1.091 / 1.091 / 1.099 / 1.097 / 1.110 / 1.114;
+  // 500,000 bodies: 0.692 / 0.601 / - / 0.604 / - / 0.605; 2M: 2.252 / 2.187 / - / 2.177 / - / 2.178; theta 0.3 at 1M:
+  // 3.533 / 3.245 / - / 3.220 / - / 3.232 — profiles/r04_drain/).
+  static const int env_tail = study_env("BH_FORCE_TAIL") ? atoi(study_env("BH_FORCE_TAIL")) : -1;
+  const long long T = env_tail >= 0 ? env_tail : (long long)c->num_cus * 4 * kTailWaves / 3;
+  p.group = force_group(c, hi - lo);
+  if (e == force_entry::pass) {
+    // a wave pops one child block per opened cell: no wave of a well-formed pool can pop more blocks than the pool has
+    // records, so kTraversalBudget never fires on valid data and always ends a walk over a cycle
+    p.budget = true;
+    const long long G = ((long long)(hi - lo) + 63) / 64;  // 64-body groups of this launch
+    const bool aligned = lo % 256 == 0;  // the launch's groups are the context's groups
+    if (c->p.force_variant == 0 && c->p.force_coop != 1 && aligned) {
+      // big jobs first, short jobs last (force_mixed_kernel), as in bh_step: every pass of the domain-decomposed step
+      // is a launch with its own drain — decided from the groups of THIS launch, not of the context
+      if (c->p.force_coop == 0 && p.group == 64 && G > 2 * T) return plan_mixed(c, p, mixed_bulk_groups(G, T), G);
+      // ... and a pass that would not fill the GPU is cooperative throughout (force_coop_kernel from the top-tree root:
+      // the strong-scaling sizes, 1M bodies over 8 ranks = 125,000 per rank; the first part of a partial two-pass
+      // step), K from the groups of THIS launch
+      if (c->p.force_group == 0 || c->p.force_group == 64) return plan_coop(c, p, lo, 64, coop_waves(c, G));
+    }
+    return plan_one_wave(c, p, lo, hi, resolve_xcd_mode(c, hi - lo, p.group));
+  }
+  // Which walk a group gets depends on the context's body count only (force_coop, force_bulk_bodies): bodies
+  // [0, bulk) in 64-body groups by one wave each, bodies [bulk, n) by K waves per group.
+  const int K = force_coop(c, p.group, T);
+  p.bulk = force_bulk_bodies(c, p.group, K, T);
+  p.count = e == force_entry::counting;
+  p.grid = (hi - lo + 255) / 256;
+  p.block = 256;
+  // the frec pool = tree digests + one digest slot per body (bh_internal.h).  The fast kernels address records with
+  // 32-bit byte offsets: pool = 5n + 16 records of 32 B < 4 GiB, i.e. up to ~26.8M bodies per context; beyond that the
+  // generic kernel does the same arithmetic on the canonical records (INTEGRATION.md notes the threshold)
+  if (c->p.literal_force && !p.count)
+    p.walk = force_walk::literal;
+  else if (p.count || c->p.strict_fp || (long long)BH_FREC_POOL(c->rec_cap, c->n) >= (1ll << 27))
+    p.walk = c->p.strict_fp ? force_walk::strict : force_walk::generic;
+  if (p.walk != force_walk::none) return p;
+  const int xcd = resolve_xcd_mode(c, hi - lo, p.group);  // the request's: also that of a one-wave remainder
+  if (p.bulk > 0 && p.bulk < c->n && lo == 0 && hi == c->n)
+    return plan_mixed(c, p, p.bulk / 64, ((long long)c->n + 63) / 64);
+  if (hi <= p.bulk) return plan_one_wave(c, p, lo, hi, xcd);
+  if (rest && lo < p.bulk) *rest = plan_one_wave(c, p, lo, p.bulk, xcd);
+  // groups of [max(lo, bulk), hi) by K waves each (a mixed launch's tail: by four)
+  return plan_coop(c, p, lo > p.bulk ? lo : p.bulk, p.group, K > 1 ? K : kMixedK);
+}
+
+template <bool PF>
+static auto fast_instance(bool budget, bool fuse, bool trace) {
+  return budget ? force_fast_kernel<0, true, PF>
+                : (fuse ? force_fast_kernel<0, false, PF, true>
+                        : (trace ? force_fast_kernel<0, false, PF, false, true> : force_fast_kernel<0, false, PF>));
+}
+
+// Makes the launch p describes.  acc: where the accelerations go; root: the pool record every walk starts from;
+// fuse: the FUSE instance with these arguments (null: none); hold: bh_devinfo.dd_hold of a decomposed pass (null:
+// none); trace: the TRACE instance, one row per wave there (null: none).  Only the walks of a single context have
+// TRACE instances, and the fast walks FUSE ones only outside a decomposed pass.
+static hipError_t force_launch(const bh_ctx* c, const force_plan& p, hipStream_t s, float4* acc, int root,
+                               const bh_fuse_args* fuse, const int* hold, u32* trace) {
+  bh_fuse_args fz = fuse ? *fuse : bh_fuse_args{};
+  fz.trace = trace;
+  const float* frec = (const float*)c->frec;
+  const float4* posm = c->posm[c->cur];
+  const float G = c->p.G, e2 = c->p.eps2;
+  switch (p.walk) {
+    case force_walk::none: return hipSuccess;
+    case force_walk::literal:
+      force_literal_kernel<<<p.grid, p.block, 0, s>>>(c->rec, posm, acc, p.lo, p.hi, G, e2);
+      break;
+    case force_walk::strict:
+    case force_walk::generic: {
+      auto k = p.walk == force_walk::strict ? (p.count ? force_kernel<true, true> : force_kernel<true, false>)
+                                            : (p.count ? force_kernel<false, true> : force_kernel<false, false>);
+      k<<<p.grid, p.block, 0, s>>>(c->rec, posm, acc, p.lo, p.hi, G, c->p.theta, e2, p.count ? c->cV : nullptr,
+                                   p.count ? c->cO : nullptr, p.count ? c->cP : nullptr, c->info);
+      break;
+    }
+    case force_walk::fast:
+    case force_walk::fast_pf:
+    case force_walk::fast_v1: {
+      auto k = p.walk == force_walk::fast_v1 ? (p.budget ? force_fast_kernel<1, true> : force_fast_kernel<1, false>)
+               : p.walk == force_walk::fast_pf ? fast_instance<true>(p.budget, fuse, trace)
+                                               : fast_instance<false>(p.budget, fuse, trace);
+      k<<<p.grid, p.block, p.lds, s>>>(frec, posm, acc, p.lo, p.hi, G, e2, p.xcd, c->info, root,
+                                       p.budget ? kTraversalBudget : 0, p.group, fz, hold);
+      break;
+    }
+    case force_walk::coop: {
+      auto k = fuse ? force_coop_kernel<true> : (trace ? force_coop_kernel<false, true> : force_coop_kernel<false>);
+      k<<<p.grid, p.block, p.lds, s>>>(frec, posm, acc, p.lo, p.hi, e2, p.xcd, c->info, p.group, fz, root, hold);
+      break;
+    }
+    case force_walk::mixed: {
+      auto k = fuse ? (p.budget ? force_mixed_kernel<true, true> : force_mixed_kernel<true>)
+                    : (trace ? force_mixed_kernel<false, false, true>
+                             : (p.budget ? force_mixed_kernel<false, true> : force_mixed_kernel<false>));
+      // (lo / 64: the launch covers the context's groups from there — lo is a multiple of 256 in a pass, 0 otherwise)
+      k<<<p.grid, p.block, p.lds, s>>>(frec, posm, acc, p.hi, e2, p.xcd, c->info, p.nbulk, p.gb, fz, root, p.lo / 64,
+                                       hold);
+      break;
+    }
+  }
+  return hipGetLastError();
 }
 
 // bh_force_range: a slab [lo, hi) gets the bits of the full launch only if the groups it forms are the full launch's
@@ -1536,209 +1697,46 @@ static int mixed_tail_grid(int mmode, int tail) {
 // any lo — the result does not depend on the group.)
 bool bhk_force_range_aligned(const bh_ctx* c, int lo) {
   if (c->p.strict_fp || c->p.literal_force || c->p.force_variant != 0) return true;
-  const int group = force_group(c, c->n);
-  const int K = force_coop(c, group);
-  const int bulk = force_bulk_bodies(c, group, K);
-  if (bulk >= c->n) return true;  // one wave per group throughout
-  return lo <= bulk || (lo - bulk) % group == 0;
+  const force_plan p = plan_force(c, 0, c->n, force_entry::single);
+  return p.bulk >= c->n || lo <= p.bulk || (lo - p.bulk) % p.group == 0;
 }
 
 // fuse_integrate (bh_step): the launch may also integrate the bodies and fold the next step's cube into
-// c->bounds_next (force_fast_kernel FUSE); *fused tells whether it did (only the hand-scheduled walk over all bodies)
+// c->bounds_next (FUSE instances); *fused tells whether it did (only the hand-scheduled walks over all bodies)
 hipError_t bhk_force(bh_ctx* c, int lo, int hi, bool count, bool fuse_integrate, bool* fused) {
   if (fused) *fused = false;
-  if (hi <= lo) return hipSuccess;
-  const int blocks = (hi - lo + 255) / 256;
-  const bh_node* rec = c->rec;
-  const float4* posm = c->posm[c->cur];
-  const float G = c->p.G, th = c->p.theta, e2 = c->p.eps2;
-  if (c->p.literal_force && !count) {
-    force_literal_kernel<<<blocks, 256, 0, c->stream>>>(rec, posm, c->acc, lo, hi, G, e2);
-    return hipGetLastError();
-  }
-  if (count) {
-    if (c->p.strict_fp)
-      force_kernel<true, true><<<blocks, 256, 0, c->stream>>>(rec, posm, c->acc, lo, hi, G, th, e2, c->cV, c->cO, c->cP, c->info);
-    else
-      force_kernel<false, true><<<blocks, 256, 0, c->stream>>>(rec, posm, c->acc, lo, hi, G, th, e2, c->cV, c->cO, c->cP, c->info);
-  } else {
-    if (c->p.strict_fp)
-      force_kernel<true, false><<<blocks, 256, 0, c->stream>>>(rec, posm, c->acc, lo, hi, G, th, e2, nullptr, nullptr, nullptr, c->info);
-    else {
-      // the frec pool = tree digests + one digest slot per body (bh_internal.h)
-      if ((long long)BH_FREC_POOL(c->rec_cap, c->n) >= (1ll << 27)) {
-        // the fast kernel addresses records with 32-bit byte offsets: pool = 5n + 16 records of 32 B < 4 GiB,
-        // i.e. up to ~26.8M bodies per context; beyond that the generic kernel does the same arithmetic on the
-        // canonical records (INTEGRATION.md notes the threshold)
-        force_kernel<false, false><<<blocks, 256, 0, c->stream>>>(rec, posm, c->acc, lo, hi, G, th, e2, nullptr, nullptr, nullptr, c->info);
-        return hipGetLastError();
-      }
-      int tpb = c->p.force_block;  // 64, 128 or 256 threads per workgroup (0 = default)
-      if (tpb != 64 && tpb != 128 && tpb != 256) tpb = BH_FORCE_BLOCK_DEFAULT;
-      const int group = force_group(c, hi - lo);
-      const int mode = resolve_xcd_mode(c, hi - lo, group);
-      int g2 = ((hi - lo + group - 1) / group * 64 + tpb - 1) / tpb;
-      if (mode == 2) g2 = (g2 + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-#ifdef BH_STUDY  // design-study builds only (tools/mkvariant.sh study -DBH_STUDY): bounded walk / occupancy cap
-      static const bool debug_budget = getenv("BH_FORCE_BUDGET") != nullptr;
-      static const int lds_pad = getenv("BH_FORCE_LDS") ? atoi(getenv("BH_FORCE_LDS")) : 0;
-#else
-      constexpr bool debug_budget = false;
-      constexpr int lds_pad = 0;
-#endif
-      const int waves = (hi - lo + group - 1) / group;
-      // Which walk a group gets depends on the context's body count only (force_coop, force_bulk_bodies): bodies
-      // [0, bulk) in 64-body groups by one wave each, bodies [bulk, n) by K waves per group.
-      const int K = force_coop(c, group);
-      const int bulk = debug_budget ? c->n : force_bulk_bodies(c, group, K);
-      const int subsh = force_coop_subsh(c);
-      const bool full = lo == 0 && hi == c->n;
-      const bool fuse = fuse_integrate && fused && full && (c->n + group - 1) / group <= c->fuse_waves;
-      const bh_fuse_args fz{c->posm[c->cur], c->velid[c->cur], c->p.dt,       c->p.max_speed, c->fuse_rows,
-                            c->fuse_rows + (size_t)c->fuse_waves * 6, c->fuse_cnt, c->bounds_next, waves};
-      if (bulk > 0 && bulk < c->n && full) {  // big jobs first, short jobs last: force_mixed_kernel
-        const int gb = bulk / 64, tail = (c->n - bulk + 63) / 64;
-        const int mmode = resolve_xcd_mode(c, bulk, 64);
-        int nbulk = gb / 4;
-        if (mmode == 2) nbulk = (nbulk + 8 * kMixedRun - 1) / (8 * kMixedRun) * (8 * kMixedRun);
-#define BH_MIXED(F, S)                                                                                        \
-  force_mixed_kernel<F, S><<<nbulk + mixed_tail_grid(mmode, tail), 256, 0, c->stream>>>((const float*)c->frec, posm, c->acc, hi, e2, mmode, \
-                                                                c->info, nbulk, gb, F ? fz : bh_fuse_args{})
-#ifdef BH_STUDY
-        if (fuse) {
-          if (subsh == 11) BH_MIXED(true, 11); else if (subsh == 12) BH_MIXED(true, 12); else BH_MIXED(true, 13);
-        } else {
-          if (subsh == 11) BH_MIXED(false, 11); else if (subsh == 12) BH_MIXED(false, 12); else BH_MIXED(false, 13);
-        }
-#else
-        (void)subsh;
-        if (fuse) BH_MIXED(true, 11); else BH_MIXED(false, 11);
-#endif
-#undef BH_MIXED
-        if (fuse) *fused = true;
-        return hipGetLastError();
-      }
-      if (hi > bulk) {  // groups of [max(lo, bulk), hi) by Kc waves each (force_coop_kernel): one workgroup per group
-        const int clo = lo > bulk ? lo : bulk;
-        const int Kc = K > 1 ? K : kMixedK;
-        int gc = (hi - clo + group - 1) / group;
-        const int cmode = resolve_xcd_mode(c, hi - clo, group);
-        if (cmode == 2) gc = (gc + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-#define BH_COOP(F, S)                                                                                         \
-  force_coop_kernel<F, S><<<gc, Kc * 64, coop_lds_bytes(Kc, S), c->stream>>>(                                  \
-      (const float*)c->frec, posm, c->acc, clo, hi, e2, cmode, c->info, group, F ? fz : bh_fuse_args{})
-#ifdef BH_STUDY
-        if (fuse && bulk == 0) {
-          if (subsh == 11) BH_COOP(true, 11); else if (subsh == 12) BH_COOP(true, 12); else BH_COOP(true, 13);
-        } else {
-          if (subsh == 11) BH_COOP(false, 11); else if (subsh == 12) BH_COOP(false, 12); else BH_COOP(false, 13);
-        }
-#else
-        if (fuse && bulk == 0) BH_COOP(true, 11); else BH_COOP(false, 11);
-#endif
-#undef BH_COOP
-        if (fuse && bulk == 0) *fused = true;
-        if (lo >= bulk) return hipGetLastError();
-        hi = bulk;  // the rest by one wave per group, below
-        g2 = ((hi - lo + group - 1) / group * 64 + tpb - 1) / tpb;
-        if (mode == 2) g2 = (g2 + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-        fuse_integrate = false;
-      }
-      if (fuse_integrate && fuse && !debug_budget && c->p.force_variant == 0) {
-        if (hi - lo <= kPrefetchMaxBodies)
-          force_fast_kernel<0, false, true, true><<<g2, tpb, 0, c->stream>>>(
-              (const float*)c->frec, posm, c->acc, lo, hi, G, e2, mode, c->info, 0, 0, group, fz);
-        else
-          force_fast_kernel<0, false, false, true><<<g2, tpb, (size_t)lds_pad, c->stream>>>(
-              (const float*)c->frec, posm, c->acc, lo, hi, G, e2, mode, c->info, 0, 0, group, fz);
-        *fused = true;
-        return hipGetLastError();
-      }
-      if (debug_budget)
-        force_fast_kernel<0, true><<<g2, tpb, 0, c->stream>>>((const float*)c->frec, posm, c->acc, lo, hi, G, e2,
-                                                              mode, c->info, 0, kTraversalBudget, group);
-      else if (c->p.force_variant == 1)
-        force_fast_kernel<1, false><<<g2, tpb, 0, c->stream>>>((const float*)c->frec, posm, c->acc, lo, hi, G, e2,
-                                                               mode, c->info, 0, 0, group);
-      else if (hi - lo <= kPrefetchMaxBodies)
-        force_fast_kernel<0, false, true><<<g2, tpb, (size_t)lds_pad, c->stream>>>((const float*)c->frec, posm, c->acc,
-                                                                                   lo, hi, G, e2, mode, c->info, 0, 0, group);
-      else  // lds_pad (BH_STUDY builds, tools/occupancy_ab.sh): dynamic LDS bytes per workgroup cap the waves per CU
-        force_fast_kernel<0, false><<<g2, tpb, (size_t)lds_pad, c->stream>>>((const float*)c->frec, posm, c->acc, lo,
-                                                                             hi, G, e2, mode, c->info, 0, 0, group);
-    }
-  }
-  return hipGetLastError();
+  force_plan rest;
+  const force_plan p = plan_force(c, lo, hi, count ? force_entry::counting : force_entry::single, &rest);
+  const bool fuse = fuse_integrate && fused && p.hand() && lo == 0 && hi == c->n && p.groups() <= c->fuse_waves;
+  const bh_fuse_args fz{c->posm[c->cur], c->velid[c->cur], c->p.dt,       c->p.max_speed, c->fuse_rows,
+                        c->fuse_rows + (size_t)c->fuse_waves * 6, c->fuse_cnt, c->bounds_next, fuse ? p.groups() : 0};
+  if (fuse) *fused = true;
+  const hipError_t e = force_launch(c, p, c->stream, c->acc, 0, fuse ? &fz : nullptr, nullptr, nullptr);
+  return e == hipSuccess ? force_launch(c, rest, c->stream, c->acc, 0, nullptr, nullptr, nullptr) : e;
 }
 
 // Measurement: the launch bh_step would make for all bodies (same kernel, same grid, same placement; not fused with
 // the integrate step), with one trace row per wave (trace_row).  *rows = rows written (<= cap_rows, else nothing runs).
 hipError_t bhk_force_trace(bh_ctx* c, u32* trace, int cap_rows, int* rows) {
   *rows = 0;
-  if (c->p.strict_fp || c->p.literal_force || c->p.force_variant != 0 || c->dd ||
-      (long long)BH_FREC_POOL(c->rec_cap, c->n) >= (1ll << 27))
-    return hipSuccess;  // no trace for the other walks
-  const int n = c->n, group = force_group(c, n);
-  const int K = force_coop(c, group), bulk = force_bulk_bodies(c, group, K);
-  const int waves = (n + group - 1) / group;
-  const float4* posm = c->posm[c->cur];
-  bh_fuse_args fz{};
-  fz.trace = trace;
-  if (bulk > 0 && bulk < n) {
-    const int gb = bulk / 64, tail = (n - bulk + 63) / 64;
-    if (gb + kMixedK * tail > cap_rows) return hipSuccess;
-    const int mmode = resolve_xcd_mode(c, bulk, 64);
-    int nbulk = gb / 4;
-    if (mmode == 2) nbulk = (nbulk + 8 * kMixedRun - 1) / (8 * kMixedRun) * (8 * kMixedRun);
-    force_mixed_kernel<false, 11, false, true><<<nbulk + mixed_tail_grid(mmode, tail), 256, 0, c->stream>>>(
-        (const float*)c->frec, posm, c->acc, n, c->p.eps2, mmode, c->info, nbulk, gb, fz);
-    *rows = gb + kMixedK * tail;
-  } else if (bulk == 0) {
-    if (waves * K > cap_rows) return hipSuccess;
-    int gc = waves;
-    const int cmode = resolve_xcd_mode(c, n, group);
-    if (cmode == 2) gc = (gc + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-    force_coop_kernel<false, 11, true><<<gc, K * 64, coop_lds_bytes(K, 11), c->stream>>>(
-        (const float*)c->frec, posm, c->acc, 0, n, c->p.eps2, cmode, c->info, group, fz);
-    *rows = waves * K;
-  } else {
-    if (waves > cap_rows) return hipSuccess;
-    int tpb = c->p.force_block;
-    if (tpb != 64 && tpb != 128 && tpb != 256) tpb = BH_FORCE_BLOCK_DEFAULT;
-    const int mode = resolve_xcd_mode(c, n, group);
-    int g2 = (waves * 64 + tpb - 1) / tpb;
-    if (mode == 2) g2 = (g2 + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-    if (n <= kPrefetchMaxBodies)
-      force_fast_kernel<0, false, true, false, true><<<g2, tpb, 0, c->stream>>>(
-          (const float*)c->frec, posm, c->acc, 0, n, c->p.G, c->p.eps2, mode, c->info, 0, 0, group, fz);
-    else
-      force_fast_kernel<0, false, false, false, true><<<g2, tpb, 0, c->stream>>>(
-          (const float*)c->frec, posm, c->acc, 0, n, c->p.G, c->p.eps2, mode, c->info, 0, 0, group, fz);
-    *rows = waves;
-  }
-  return hipGetLastError();
+  const force_plan p = plan_force(c, 0, c->n, force_entry::single);
+  if (c->dd || !p.hand() || p.rows() > cap_rows) return hipSuccess;  // no trace for the other walks
+  *rows = p.rows();
+  return force_launch(c, p, c->stream, c->acc, 0, nullptr, nullptr, trace);
 }
 
 // the instruction stream of the launch bhk_force would make: the same bodies per wave (force_group) and the same
 // instance of the walk — with the scalar-cache prefetch and every stack entry in the lanes up to kPrefetchMaxBodies
 // bodies, with the stack top in scalar registers above (round-3 review: the small configurations were counted with
 // the other instance)
-int bhk_force_walk_rows(const bh_ctx* c) {
-  const int group = force_group(c, c->n);
-  return (c->n + group - 1) / group;
-}
+int bhk_force_walk_rows(const bh_ctx* c) { return plan_force(c, 0, c->n, force_entry::single).groups(); }
 hipError_t bhk_force_walk_stats(bh_ctx* c, u32* rows /* [bhk_force_walk_rows][BH_WALK_ROW], device */, int root) {
-  int tpb = c->p.force_block;
-  if (tpb != 64 && tpb != 128 && tpb != 256) tpb = BH_FORCE_BLOCK_DEFAULT;
+  const force_plan p = plan_force(c, 0, c->n, force_entry::single);
+  const int tpb = force_block(c);
   const int mode = (c->p.xcd_mode == 1) ? 1 : 0;  // one row per wave in launch order: no grid padding here
-  const int group = force_group(c, c->n);
-  const int g2 = (bhk_force_walk_rows(c) * 64 + tpb - 1) / tpb;
-  if (c->n <= kPrefetchMaxBodies)
-    force_walk_stats_kernel<true><<<g2, tpb, 0, c->stream>>>((const float*)c->frec, c->posm[c->cur], c->n, c->p.eps2,
-                                                             mode, group, rows, root);
-  else
-    force_walk_stats_kernel<false><<<g2, tpb, 0, c->stream>>>((const float*)c->frec, c->posm[c->cur], c->n, c->p.eps2,
-                                                              mode, group, rows, root);
+  auto k = c->n <= kPrefetchMaxBodies ? force_walk_stats_kernel<true> : force_walk_stats_kernel<false>;
+  k<<<(p.groups() * 64 + tpb - 1) / tpb, tpb, 0, c->stream>>>((const float*)c->frec, c->posm[c->cur], c->n,
+                                                             c->p.eps2, mode, p.group, rows, root);
   return hipGetLastError();
 }
 
@@ -1747,79 +1745,22 @@ hipError_t bhk_force_walk_stats(bh_ctx* c, u32* rows /* [bhk_force_walk_rows][BH
 // fuse_add: non-null = this is the LAST pass of the step (every earlier pass has finished): the launch adds those
 // accelerations (null pointer value (float4*)1: there were none), integrates the bodies and folds this rank's min / max
 // into c->dd_minmax (force_mixed_kernel FUSE); *fused tells whether it did (large local body counts only).
-hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t stream, float4* acc, const float4* fuse_add,
-                          bool fuse, bool* fused, int fold_groups) {
+// hold: bh_devinfo.dd_hold — the decomposed step's launches are enqueued before the host knows whether the X4 behind
+// them fits (bh_dd.hip)
+hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t stream, float4* acc, const int* hold,
+                          const float4* fuse_add, bool fuse, bool* fused, int fold_groups) {
+  if (fused) *fused = false;
+  const force_plan p = plan_force(c, lo, hi, force_entry::pass);
   // fold_groups: a step whose bodies are covered by SEVERAL fused launches (partial two-pass step: bh_dd.hip) shares
   // one min / max fold between them — the number of groups of all of them (0: this launch alone)
-  if (fused) *fused = false;
-  if (hi <= lo) return hipSuccess;
-  int tpb = c->p.force_block;
-  if (tpb != 64 && tpb != 128 && tpb != 256) tpb = BH_FORCE_BLOCK_DEFAULT;
-  const int group = force_group(c, hi - lo);
-  const int mode = resolve_xcd_mode(c, hi - lo, group);
-  int g2 = ((hi - lo + group - 1) / group * 64 + tpb - 1) / tpb;
-  if (mode == 2) g2 = (g2 + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-  // a wave pops one child block per opened cell: no wave of a well-formed pool can pop more blocks than
-  // the pool has records, so this bound never fires on valid data and always ends a walk over a cycle
-  // (the decomposed step's launches are enqueued before the host knows whether the X4 behind them fits: bh_dd.hip)
-  const int* hold = c->dd ? &c->info->dd_hold : nullptr;
-  const int budget = kTraversalBudget;
-  const bool aligned = lo % 256 == 0;  // the launch's groups are the context's groups
-  const long long G = ((long long)(hi - lo) + 63) / 64;  // groups of this launch
-  const long long Gall = fold_groups > 0 ? fold_groups : G;
-  const bool can_fuse = fuse && fused && (fold_groups > 0 || (lo == 0 && hi == c->n)) && (int)Gall <= c->fuse_waves;
-  bh_fuse_args fz{c->posm[c->cur], c->velid[c->cur], c->p.dt,       c->p.max_speed, c->fuse_rows,
-                  c->fuse_rows + (size_t)c->fuse_waves * 6, c->fuse_cnt, c->dd_minmax, (int)Gall};
-  fz.acc_add = fuse_add;
-  fz.raw = 1;
-  // big jobs first, short jobs last (force_mixed_kernel), as in bh_step: every pass of the domain-decomposed step is
-  // a launch with its own drain
-  if (c->p.force_variant == 0 && c->p.force_coop == 0 && aligned && group == 64 && G > 2 * force_tail_groups(c)) {
-    const int gb = (int)((G - force_tail_groups(c)) & ~3ll), tail = (int)(G - gb);
-    const int mmode = resolve_xcd_mode(c, gb * 64, 64);
-    int nbulk = gb / 4;
-    if (mmode == 2) nbulk = (nbulk + 8 * kMixedRun - 1) / (8 * kMixedRun) * (8 * kMixedRun);
-    if (can_fuse) {
-      force_mixed_kernel<true, 11, true><<<nbulk + mixed_tail_grid(mmode, tail), 256, 0, stream>>>(
-          (const float*)c->frec, c->posm[c->cur], acc, hi, c->p.eps2, mmode, c->info, nbulk, gb, fz, root, lo / 64, hold);
-      *fused = true;
-      return hipGetLastError();
-    }
-    force_mixed_kernel<false, 11, true><<<nbulk + mixed_tail_grid(mmode, tail), 256, 0, stream>>>(
-        (const float*)c->frec, c->posm[c->cur], acc, hi, c->p.eps2, mmode, c->info, nbulk, gb, bh_fuse_args{}, root,
-        lo / 64, hold);
-    return hipGetLastError();
-  }
-  // ... and a pass that would not fill the GPU is cooperative throughout (force_coop_kernel from the top-tree root:
-  // the strong-scaling sizes, 1M bodies over 8 ranks = 125,000 per rank; the first part of a partial two-pass step),
-  // K as in bh_step
-  if (c->p.force_variant == 0 && c->p.force_coop != 1 && aligned && (c->p.force_group == 0 || c->p.force_group == 64)) {
-    const int K = c->p.force_coop >= 2 && c->p.force_coop <= kCoopMaxK
-                      ? c->p.force_coop
-                      : (G * kCoopMaxK <= (long long)c->num_cus * 4 * kWalkWaves ? kCoopMaxK : 4);
-    const int cmode = resolve_xcd_mode(c, hi - lo, 64);
-    int gc = (int)G;
-    if (cmode == 2) gc = (gc + 8 * kXcdRun - 1) / (8 * kXcdRun) * (8 * kXcdRun);
-    if (can_fuse) {
-      force_coop_kernel<true, 11><<<gc, K * 64, coop_lds_bytes(K, 11), stream>>>(
-          (const float*)c->frec, c->posm[c->cur], acc, lo, hi, c->p.eps2, cmode, c->info, 64, fz, root, hold);
-      *fused = true;
-      return hipGetLastError();
-    }
-    force_coop_kernel<false, 11><<<gc, K * 64, coop_lds_bytes(K, 11), stream>>>(
-        (const float*)c->frec, c->posm[c->cur], acc, lo, hi, c->p.eps2, cmode, c->info, 64, bh_fuse_args{}, root, hold);
-    return hipGetLastError();
-  }
-  if (c->p.force_variant == 1)
-    force_fast_kernel<1, true><<<g2, tpb, 0, stream>>>((const float*)c->frec, c->posm[c->cur], acc, lo, hi, c->p.G,
-                                                       c->p.eps2, mode, c->info, root, budget, group, bh_fuse_args{}, hold);
-  else if (hi - lo <= kPrefetchMaxBodies)
-    force_fast_kernel<0, true, true><<<g2, tpb, 0, stream>>>((const float*)c->frec, c->posm[c->cur], acc, lo, hi,
-                                                             c->p.G, c->p.eps2, mode, c->info, root, budget, group, bh_fuse_args{}, hold);
-  else
-    force_fast_kernel<0, true><<<g2, tpb, 0, stream>>>((const float*)c->frec, c->posm[c->cur], acc, lo, hi, c->p.G,
-                                                       c->p.eps2, mode, c->info, root, budget, group, bh_fuse_args{}, hold);
-  return hipGetLastError();
+  const int groups = fold_groups > 0 ? fold_groups : (hi - lo + 63) / 64;
+  const bool fz_on = fuse && fused && (p.walk == force_walk::coop || p.walk == force_walk::mixed) &&
+                     (fold_groups > 0 || (lo == 0 && hi == c->n)) && groups <= c->fuse_waves;
+  const bh_fuse_args fz{c->posm[c->cur], c->velid[c->cur], c->p.dt,  c->p.max_speed, c->fuse_rows,
+                        c->fuse_rows + (size_t)c->fuse_waves * 6, c->fuse_cnt, c->dd_minmax, groups, nullptr, fuse_add,
+                        1};  // (raw: this rank's min / max)
+  if (fz_on) *fused = true;
+  return force_launch(c, p, stream, acc, root, fz_on ? &fz : nullptr, hold, nullptr);
 }
 
 

@@ -301,7 +301,7 @@ hipError_t bhk_build(bh_ctx* c, bool pm_scan = false);  // pm_scan: + the COM pr
 hipError_t bhk_com(bh_ctx* c);
 hipError_t bhk_force(bh_ctx* c, int lo, int hi, bool count, bool fuse_integrate = false, bool* fused = nullptr);
 bool bhk_force_range_aligned(const bh_ctx* c, int lo);  // a slab starting at lo forms the full launch's groups
-hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t stream, float4* acc,
+hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t stream, float4* acc, const int* hold,
                           const float4* fuse_add = nullptr, bool fuse = false,
                           bool* fused = nullptr, int fold_groups = 0);  // fast kernel from pool record `root`
 hipError_t bhk_force_walk_stats(bh_ctx* c, u32* rows, int root = 0);  // measurement: per-wave event counters of the fast walk
