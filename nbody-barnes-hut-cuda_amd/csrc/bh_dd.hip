@@ -2326,6 +2326,10 @@ static int dd_force_local_prepare(bh_ctx* c, const void* gathered_x3) {
 // second half: the launch that fills the GPU.  after_let: behind what the main stream holds at this point (the LET
 // export) — a saturating launch of the side stream starves whatever the main stream launches after it
 // (dd_make_side_stream), so the own pass hides X4 and not the LET kernels.
+// Not held (hold null): the pass walks this rank's pieces only (top_base2: other ranks' pieces are null records), so
+// nothing in it depends on X4, and it runs once per step — a repeated X4 does not launch it again.  On the side stream
+// it is still being dispatched when dd_validate_kernel (main stream, reserved units) raises dd_hold for an X4 that does
+// not fit: groups that read the flag then would leave their bodies' accelerations stale.
 static int dd_force_local_launch(bh_ctx* c, bool after_let) {
   bh_dd_state* d = c->dd;
   hipStream_t so = d->serial ? c->stream : d->stream_own;
@@ -2333,7 +2337,7 @@ static int dd_force_local_launch(bh_ctx* c, bool after_let) {
     BH_HIP(c, hipEventRecord(d->ev_let, c->stream));
     BH_HIP(c, hipStreamWaitEvent(so, d->ev_let, 0));
   }
-  if (d->own_hi > 0) BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base2, so, c->acc, &c->info->dd_hold));
+  if (d->own_hi > 0) BH_HIP(c, bhk_force_root(c, 0, d->own_hi, d->top_base2, so, c->acc, nullptr));
   BH_HIP(c, hipEventRecord(d->ev_own, so));
   return BH_OK;
 }
@@ -2576,7 +2580,9 @@ int bh_dd_phase_force(bh_ctx* c, const void* gathered_x3, int stride, int32_t* c
   if (!counts) counts = own_counts;
   // The force launches go out BEFORE the host has looked at the X4 headers: the validation kernel takes the same
   // decision on the device (bh_devinfo.dd_hold) and a launch behind an exchange that has to be repeated — or that a rank
-  // has left — returns at once.  The host's look (a polled pinned word) then costs the step nothing.
+  // has left — returns at once.  The host's look (a polled pinned word) then costs the step nothing.  Held: every
+  // launch enqueued behind dd_validate_kernel (the remote passes, the one pass of the bodies beyond own_hi, the one
+  // pass of an unsplit step) — not the own-pieces pass launched before X4 (dd_force_local_launch).
   // (one rank in two passes: the remote pass walks nothing but the top record, and a launch that short integrates
   // slower than the streaming kernel does — 0.100 against 0.055 + 0.021 ms at 1M bodies; one pass integrates as
   // bh_step's launch does)

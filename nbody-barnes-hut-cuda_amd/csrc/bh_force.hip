@@ -950,9 +950,10 @@ __device__ __forceinline__ void trace_row(u32* tr, int row, u32 t0) {
 // Domain-decomposed step: the launch was enqueued behind an X4 whose fit the host had not yet looked at; the
 // validation kernel has (bh_devinfo.dd_hold, bh_dd.hip): the exchange is repeated, or a rank has left — nothing to
 // walk.
-// `hold` is null for every launch outside the decomposed step (no load at all); the load is issued first thing and
-// consumed after the wave's own position load has been issued, so that it adds no latency of its own to the wave's
-// start (a launch of a few dozen microseconds per workgroup shows a dependent load at its head: +1.5 % at 65,536).
+// `hold` is null for every launch outside the decomposed step and for its own-pieces pass, which does not wait for X4
+// (no load at all); the load is issued first thing and consumed after the wave's own position load has been issued,
+// so that it adds no latency of its own to the wave's start (a launch of a few dozen microseconds per workgroup shows
+// a dependent load at its head: +1.5 % at 65,536).
 __device__ __forceinline__ int force_hold_load(const int* hold) {
   return hold ? __hip_atomic_load(hold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
 }
@@ -1745,8 +1746,8 @@ hipError_t bhk_force_walk_stats(bh_ctx* c, u32* rows /* [bhk_force_walk_rows][BH
 // fuse_add: non-null = this is the LAST pass of the step (every earlier pass has finished): the launch adds those
 // accelerations (null pointer value (float4*)1: there were none), integrates the bodies and folds this rank's min / max
 // into c->dd_minmax (force_mixed_kernel FUSE); *fused tells whether it did (large local body counts only).
-// hold: bh_devinfo.dd_hold — the decomposed step's launches are enqueued before the host knows whether the X4 behind
-// them fits (bh_dd.hip)
+// hold: bh_devinfo.dd_hold — the decomposed step's launches behind X4 are enqueued before the host knows whether that
+// X4 fits (bh_dd.hip); null for the own-pieces pass, which needs nothing from X4 and is launched once per step
 hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t stream, float4* acc, const int* hold,
                           const float4* fuse_add, bool fuse, bool* fused, int fold_groups) {
   if (fused) *fused = false;

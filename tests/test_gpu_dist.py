@@ -149,6 +149,18 @@ def test_bench_two_ranks_domain_fallback_is_collective():
     assert "replicated" in out["config"]["parallelism"]
 
 
+def _same_state(res):
+    """the last step against one single-context step from the same state (tests/dd_gpu_worker.py): the first-step
+    bounds of tests/test_gpu_dd.py::check_last_step; masses bit for bit those of the initial conditions"""
+    print({k: v for k, v in res.items() if k.startswith("last_")})
+    assert res["mass_exact"], res
+    assert res["last_acc_rel_median"] < 2e-6, res
+    assert res["last_acc_rel_p9999"] < 1e-4, res
+    assert res["last_acc_rel_max"] < 2e-3, res
+    assert res["last_max_dpos"] < 1e-3, res
+    assert res["last_max_dvel"] < 5e-5, res      # (test_gpu_dd.DVEL_MAX: measured 7.6e-6 for 2 x 500,000 bodies)
+
+
 @pytest.mark.parametrize("world,split,pct", [(2, "one", 0), (3, "one", 0), (2, "two", 0), (3, "two", 100), (3, "two", 50)])
 def test_domain_stepper_multiprocess_one_gpu(world, split, pct, tmp_path):
     """the real multi-process flow of the domain-decomposed step (torch.distributed, one process per rank, every rank
@@ -169,6 +181,7 @@ def test_domain_stepper_multiprocess_one_gpu(world, split, pct, tmp_path):
     assert res["world"] == world and res["owned_once"] and res["flags"] == 0
     assert res["max_dpos"] < 5e-2, res
     assert res["acc_rel_median"] < 1e-4, res
+    _same_state(res)
 
 
 def test_domain_stepper_multiprocess_large_ranks_two_launches_at_once(tmp_path):
@@ -187,6 +200,7 @@ def test_domain_stepper_multiprocess_large_ranks_two_launches_at_once(tmp_path):
     assert res["world"] == 2 and res["owned_once"] and res["flags"] == 0
     assert res["max_dpos"] < 5e-2, res
     assert res["acc_rel_median"] < 1e-4, res
+    _same_state(res)
 
 
 def test_adaptive_form_turns_the_split_on_when_the_exchange_is_slow(tmp_path):
@@ -207,6 +221,7 @@ def test_adaptive_form_turns_the_split_on_when_the_exchange_is_slow(tmp_path):
     assert res["x4_us"] > 200 and res["split_now"] == 1, res
     assert res["max_dpos"] < 5e-2, res
     assert res["acc_rel_median"] < 1e-4, res
+    _same_state(res)
 
 
 def test_bh_bench_whole_node_frame_loop_on_one_gpu():
