@@ -66,6 +66,8 @@ def lib():
         L.bho_integrate.argtypes = [_F, _F, _F, C.c_int, C.POINTER(Params)]
         L.bho_direct_f64.argtypes = [_F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                      C.POINTER(C.c_double), C.c_int]
+        L.bho_force_f64.argtypes = [C.c_void_p, _F, _I32, C.c_int, C.POINTER(Params), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), _U32, _U32, _U32, _U32, C.POINTER(C.c_double), C.c_int]
         L.bho_create.argtypes = [C.c_int, C.POINTER(Params)]
         L.bho_create.restype = C.c_void_p
         L.bho_destroy.argtypes = [C.c_void_p]
@@ -218,6 +220,29 @@ def direct_f64(xyzm, G, eps2, lo=0, hi=None, nthreads=0):
     out = np.zeros((hi - lo, 3), np.float64)
     lib().bho_direct_f64(_fp(xyzm), n, int(lo), int(hi), C.c_float(G), C.c_float(eps2),
                          out.ctypes.data_as(C.POINTER(C.c_double)), int(nthreads))
+    return out
+
+
+def force_f64(rec, xyzm, p, idx=None, nthreads=0):
+    """fp64 walk of the tree `rec` (NODE_DTYPE: build_tree + com, or Engine.download_tree()) over the sorted bodies
+    xyzm, by force()'s rules with the MAC decided exactly (bho_force_f64).  idx: the sorted indices of the bodies
+    to evaluate (None: all).  -> dict of per-row arrays: idx, acc (fp64, [nb, 3]), sabs (sum of |term|), k (terms),
+    V, O, P (as force() counts them) and margin (min over the cells decided of |theta^2 (d2 + eps2) - s^2| / s^2)."""
+    rec = np.ascontiguousarray(rec, dtype=NODE_DTYPE)
+    xyzm = _f(xyzm)
+    n = xyzm.shape[0]
+    idx = np.arange(n, dtype=np.int32) if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+    if len(idx) and (idx.min() < 0 or idx.max() >= n):
+        raise IndexError("body index out of range")
+    nb = len(idx)
+    D = C.POINTER(C.c_double)
+    out = dict(idx=idx, acc=np.zeros((nb, 3), np.float64), sabs=np.zeros(nb, np.float64),
+               k=np.zeros(nb, np.uint32), V=np.zeros(nb, np.uint32), O=np.zeros(nb, np.uint32),
+               P=np.zeros(nb, np.uint32), margin=np.zeros(nb, np.float64))
+    lib().bho_force_f64(rec.ctypes.data, _fp(xyzm), idx.ctypes.data_as(_I32), nb, C.byref(p),
+                        out["acc"].ctypes.data_as(D), out["sabs"].ctypes.data_as(D),
+                        *[out[c].ctypes.data_as(_U32) for c in ("k", "V", "O", "P")],
+                        out["margin"].ctypes.data_as(D), int(nthreads))
     return out
 
 

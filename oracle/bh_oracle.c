@@ -669,6 +669,105 @@ void bho_direct_f64(const float* xyzm, int n, int lo, int hi, float G, float eps
   }
 }
 
+/* ------------------------------------------------------------------ fp64 walk of a given tree */
+/* The checker of the fp32 walks: the same tree, the same rules as bho_force (m <= 0 skipped, a body always
+   accepted, an unsplit cell body by body), summed in fp64 from the fp32 inputs, the MAC decided exactly:
+   accept iff s^2 < theta^2 * (d2 + eps2) (d2 exact in fp64 up to one rounding).  Per body it also returns
+   what an error model of an fp32 walk needs: k (terms summed, zero ones included), sum|term|, and the MAC
+   margin, min over the cells it decided of |theta^2 (d2 + eps2) - s^2| / s^2 (a cell with s = 0 decides
+   the same in any precision and does not count).  An fp32 walk may decide a cell of margin ~1e-6 the
+   other way; one of margin 1e-5 (~170 u) it may not. */
+typedef struct {
+  const bho_node* rec;
+  const float* xyzm;
+  double px, py, pz, G, th2, eps2;
+  double ax, ay, az, sabs, margin;
+  uint32_t k, V, O, P;
+} f64ctx;
+
+static void f64_term(f64ctx* c, float cx, float cy, float cz, float m) {
+  const double dx = (double)cx - c->px, dy = (double)cy - c->py, dz = (double)cz - c->pz;
+  const double d2 = dx * dx + dy * dy + dz * dz;
+  const double r2 = d2 + c->eps2;
+  const double f = c->G * (double)m / (r2 * sqrt(r2));
+  c->ax += f * dx;
+  c->ay += f * dy;
+  c->az += f * dz;
+  c->sabs += f * sqrt(d2);
+  c->k++;
+}
+
+static void f64_walk(f64ctx* c) {
+  int nxt[64], left[64], sp = 1; /* as walk_pre_iter */
+  nxt[0] = 0; left[0] = 1;
+  while (sp > 0) {
+    const int e = nxt[sp - 1]++;
+    if (--left[sp - 1] == 0) sp--;
+    const bho_node* r = &c->rec[e];
+    if (r->m <= 0.0f) continue;
+    if (r->kind == BHO_KIND_BODY) {
+      f64_term(c, r->x, r->y, r->z, r->m);
+      c->P++;
+      continue;
+    }
+    c->V++;
+    const double dx = (double)r->x - c->px, dy = (double)r->y - c->py, dz = (double)r->z - c->pz;
+    const double s2 = (double)r->s * (double)r->s;
+    const double lhs = c->th2 * (dx * dx + dy * dy + dz * dz + c->eps2);
+    if (s2 > 0.0) {
+      const double mg = fabs(lhs - s2) / s2;
+      if (mg < c->margin) c->margin = mg;
+    }
+    if (s2 < lhs) {
+      f64_term(c, r->x, r->y, r->z, r->m);
+      continue;
+    }
+    c->O++;
+    if (r->kind == BHO_KIND_INTERNAL) {
+      nxt[sp] = r->first; left[sp] = r->count; sp++;
+    } else {
+      for (int b = r->first; b < r->first + r->count; b++) {
+        const float* q = &c->xyzm[4 * (size_t)b];
+        if (q[3] <= 0.0f) continue;
+        f64_term(c, q[0], q[1], q[2], q[3]);
+        c->P++;
+      }
+    }
+  }
+}
+
+void bho_force_f64(const bho_node* rec, const float* xyzm, const int32_t* idx, int nb, const bho_params* p,
+                   double* acc3, double* sabs, uint32_t* k, uint32_t* V, uint32_t* O, uint32_t* P, double* margin,
+                   int nthreads) {
+  if (nthreads < 1) nthreads = omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nthreads)
+  for (int j = 0; j < nb; j++) {
+    const int i = idx ? idx[j] : j;
+    f64ctx c;
+    c.rec = rec;
+    c.xyzm = xyzm;
+    c.px = xyzm[4 * (size_t)i + 0];
+    c.py = xyzm[4 * (size_t)i + 1];
+    c.pz = xyzm[4 * (size_t)i + 2];
+    c.G = p->G;
+    c.th2 = (double)p->theta * (double)p->theta;
+    c.eps2 = p->eps2;
+    c.ax = c.ay = c.az = c.sabs = 0.0;
+    c.margin = HUGE_VAL;
+    c.k = c.V = c.O = c.P = 0;
+    f64_walk(&c);
+    acc3[3 * (size_t)j + 0] = c.ax;
+    acc3[3 * (size_t)j + 1] = c.ay;
+    acc3[3 * (size_t)j + 2] = c.az;
+    sabs[j] = c.sabs;
+    k[j] = c.k;
+    V[j] = c.V;
+    O[j] = c.O;
+    P[j] = c.P;
+    margin[j] = c.margin;
+  }
+}
+
 /* ------------------------------------------------------------------ whole step */
 struct bho_state {
   int n;

@@ -76,6 +76,13 @@ void bho_integrate(float* xyzm, float* vel3, const float* acc4, int n, const bho
 /* fp64 direct O(n^2) sum with the same softened kernel (physics check) */
 void bho_direct_f64(const float* xyzm, int n, int lo, int hi, float G, float eps2, double* acc3,
                     int nthreads);
+/* fp64 walk of a given tree (rec in the bho_node layout: bho_build + bho_com, or the engine's downloaded tree) by
+   bho_force's rules, the MAC decided exactly in fp64.  For the nb bodies idx[j] (idx NULL: bodies 0..nb-1) -> row j:
+   acc3[3j..], sum of |term| sabs[j], terms k[j] (m > 0 ones, zero-length included), V / O / P as bho_force counts
+   them, margin[j] = min over the cells decided of |theta^2 (d2 + eps2) - s^2| / s^2 (HUGE_VAL: none) */
+void bho_force_f64(const bho_node* rec, const float* xyzm, const int32_t* idx, int nb, const bho_params* p,
+                   double* acc3, double* sabs, uint32_t* k, uint32_t* V, uint32_t* O, uint32_t* P, double* margin,
+                   int nthreads);
 
 /* ---- whole-step state machine mirroring simulationStep (ref:255-283) ---- */
 typedef struct bho_state bho_state;

@@ -11,7 +11,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import oracle_pipeline, special_ics
+from helpers import (TIE_MARGIN, check_force_f64, force_f64_errors, force_f64_flags, oracle_pipeline,
+                     special_ics)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -349,3 +350,127 @@ def test_hilbert_keys_sort_bodies_into_the_same_cells(pkg, orc):
         rec, lo, hi, ni, ml = orc.build_tree(sk, p, orc.root_edge(b))
         trees.append((len(rec), ni, ml))
     assert trees[0] == trees[1]
+
+
+# ---------------------------------------------------------------- the fp64 walk of a given tree (oracle.force_f64)
+def test_force_f64_at_theta0_is_the_direct_sum(pkg, orc):
+    """theta = 0 opens every cell: the fp64 walk sums every body once, as the fp64 direct sum does (same terms,
+    other order: a few ulp of fp64 against the sum of magnitudes)"""
+    n = 3000
+    ic = pkg.plummer(n, seed=8)
+    p = orc.params(theta=0.0)
+    o = oracle_pipeline(orc, ic, p)
+    r = orc.force_f64(o["rec"], o["xyzm"], p)
+    d = orc.direct_f64(o["xyzm"], p.G, p.eps2)
+    assert np.all(r["k"] == n) and np.all(r["P"] == n)
+    assert np.all(np.linalg.norm(r["acc"] - d, axis=1) <= 1e-13 * r["sabs"])
+    assert np.all(r["margin"] >= 1.0)   # theta = 0 decides every cell with margin 1: nothing is tied
+
+
+@pytest.mark.parametrize("theta", [0.3, 0.5, 1.0])
+def test_force_f64_counts_are_the_fp32_walks_on_non_tie_bodies(pkg, orc, theta):
+    """V / O / P of the fp64 walk == bho_force's on every non-tie body (same tree, same rules, same decisions), and a
+    sampled call returns the same rows as the full one"""
+    n = 20000
+    ic = pkg.plummer(n, seed=3)
+    p = orc.params(theta=theta)
+    o = oracle_pipeline(orc, ic, p)
+    r = orc.force_f64(o["rec"], o["xyzm"], p)
+    _, V, O, P = orc.force(o["rec"], o["xyzm"], p)
+    nt = r["margin"] >= TIE_MARGIN
+    assert nt.mean() > 0.95
+    for name, c in (("V", V), ("O", O), ("P", P)):
+        assert np.array_equal(r[name][nt], c[nt]), name
+    idx = np.arange(5, n, 97)
+    s = orc.force_f64(o["rec"], o["xyzm"], p, idx=idx)
+    assert np.array_equal(s["acc"], r["acc"][idx]) and np.array_equal(s["k"], r["k"][idx])
+
+
+@pytest.mark.parametrize("order", ["ORDER_PREORDER", "ORDER_BATCHED"])
+@pytest.mark.parametrize("n,theta", [(65536, 0.5), (65536, 0.3), (20000, 1.0)])
+def test_oracle_fp32_walk_passes_the_f64_check(pkg, orc, n, theta, order):
+    """the oracle's own fp32 walk (sequential sums, sqrtf and '/') within the per-body bound every GPU walk is held to
+    (measured: err / (sqrt(k) u sum|term|) <= 1.14); its long sequential sums have population limits of their own,
+    twice what was measured (relative median 5e-7, p99.99 1.8e-5, max 1.2e-4 over these cases)"""
+    ic = pkg.plummer(n, seed=42)
+    p = orc.params(theta=theta)
+    o = oracle_pipeline(orc, ic, p)
+    a, *_ = orc.force(o["rec"], o["xyzm"], p, getattr(orc, order))
+    r = orc.force_f64(o["rec"], o["xyzm"], p)
+    check_force_f64(a, r, f"oracle fp32 {order} n={n} theta={theta}", med=1e-6, p9999=3.6e-5, rmax=2.4e-4)
+
+
+def test_force_f64_reports_the_grid_inputs_ties(orc):
+    """bodies on a lattice of power-of-two spacing meet cells whose centre and edge are short binary fractions, so
+    some decisions sit almost exactly on the MAC boundary: the fp64 walk must report those bodies as tie bodies
+    (measured: 0.07 %, smallest margin 3.5e-7), not pass them as exact"""
+    ic = special_ics("grid", 4096, np.random.default_rng(1))
+    p = orc.params(theta=0.5)
+    o = oracle_pipeline(orc, ic, p)
+    r = orc.force_f64(o["rec"], o["xyzm"], p)
+    tie = r["margin"] < TIE_MARGIN
+    print(f"grid: {tie.mean():.2%} tie bodies, smallest margin {r['margin'].min():.3e}")
+    assert tie.any()
+    a, *_ = orc.force(o["rec"], o["xyzm"], p)
+    check_force_f64(a, r, "oracle fp32 on the grid", med=1e-6, p9999=3.6e-5, rmax=2.4e-4)
+
+
+def _mid_walk_term(orc, rec, xyzm, p, i):
+    """(the fp32 acceleration term, sorted index) of an interaction body i's walk meets halfway: a body of an opened
+    cell (the walk's BODY records and unsplit-cell bodies), computed as the fp32 walk computes it"""
+    out = []
+
+    def visit(e):
+        r = rec[e]
+        if r["m"] <= 0:
+            return
+        d = np.array([r["x"], r["y"], r["z"]], np.float32) - xyzm[i, :3]
+        dist = np.sqrt(np.float32(d @ d) + np.float32(p.eps2))
+        if r["kind"] == orc.KIND_BODY:
+            out.append(d * np.float32(p.G * r["m"] / dist ** 3))
+            return
+        if r["s"] / dist < p.theta:
+            out.append(d * np.float32(p.G * r["m"] / dist ** 3))
+            return
+        if r["kind"] == orc.KIND_INTERNAL:
+            for c in range(r["first"], r["first"] + r["count"]):
+                visit(c)
+        else:
+            for b in range(r["first"], r["first"] + r["count"]):
+                if xyzm[b, 3] > 0:
+                    d = xyzm[b, :3] - xyzm[i, :3]
+                    dist = np.sqrt(np.float32(d @ d) + np.float32(p.eps2))
+                    out.append(d * np.float32(p.G * xyzm[b, 3] / dist ** 3))
+
+    visit(0)
+    return out[len(out) // 2]
+
+
+@pytest.mark.parametrize("n,theta", [(65536, 0.5), (65536, 0.3)])
+def test_f64_check_catches_a_dropped_term(pkg, orc, n, theta):
+    """The check's sensitivity, pinned: the oracle's fp32 result with ONE mid-walk term taken out of every 500th
+    body.  A mid-walk term is often a far cell's, smaller than a body's allowance (F64_C sqrt(max(k, 48)) u sum|term|,
+    which the nearest terms dominate), so not every such body can be flagged; measured with F64_C = 1.8: 89 % (theta
+    0.5) and 78 % (theta 0.3) of the non-tie ones are, against 43 % / 29 % beyond the old relative max of 5e-4.  Held:
+    at least 70 % flagged and at least 1.5 times as many as the old limit catches, no other body flagged, and
+    check_force_f64 fails."""
+    ic = pkg.plummer(n, seed=42)
+    p = orc.params(theta=theta)
+    o = oracle_pipeline(orc, ic, p)
+    a, *_ = orc.force(o["rec"], o["xyzm"], p)
+    r = orc.force_f64(o["rec"], o["xyzm"], p)
+    mut = np.arange(250, n, 500)
+    b = a.copy()
+    for i in mut:
+        b[i, :3] -= _mid_walk_term(orc, o["rec"], o["xyzm"], p, int(i))
+    flags = force_f64_flags(b, r)
+    nt = r["margin"][mut] >= TIE_MARGIN
+    assert nt.sum() >= 0.9 * len(mut)
+    assert not np.delete(flags, mut).any()
+    _, _, rel = force_f64_errors(b, r)
+    caught, old = int(flags[mut][nt].sum()), int((rel[mut][nt] > 5e-4).sum())
+    print(f"dropped term n={n} theta={theta}: {caught} / {int(nt.sum())} non-tie bodies flagged, {old} beyond the "
+          f"old relative 5e-4")
+    assert caught >= 0.7 * nt.sum() and caught >= 1.5 * old
+    with pytest.raises(AssertionError):
+        check_force_f64(b, r, "dropped term")
