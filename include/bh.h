@@ -251,6 +251,37 @@ int bh_set_timing(bh_ctx* c, int on);
    stack / pool overflow, sort time-out, traversal limit — see BH_FLAG_*) */
 int bh_sync(bh_ctx* c);
 
+/* ---- energy diagnostics (not in the reference) ----
+ * phi_i = sum over the records r the force walk takes for body i of -G m_r / sqrt(|c_r - p_i|^2 + eps2), plus G m_i /
+ * sqrt(eps2): the walk of force_variant = 1 (same tree, same MAC d2 + eps2 > (s / theta)^2, records of mass <= 0 add 0),
+ * in fp32, with the walk's own term of the body (its record, or its share of an accepted cell that holds it) removed
+ * once at the end with the arithmetic of a walk term.  Defined for every body, mass <= 0 included; at theta = 0 it is
+ * the softened direct sum over j != i.  phi always uses the fast arithmetic on the digest records, whatever strict_fp,
+ * literal_force or force_variant say.  The system sums are accumulated in fp64 from the fp32 state, in a fixed order
+ * (no floating-point atomics: the same state gives the same bits) and describe the context's CURRENT state — after
+ * bh_step, the positions and velocities bh_download returns. */
+typedef struct bh_energy_stats {
+  double kinetic;             /* K = 1/2 sum m |v|^2                                  */
+  double potential;           /* W = 1/2 sum m phi                                    */
+  double total;               /* E = K + W                                            */
+  double mass;                /* M = sum m                                            */
+  double momentum[3];         /* P = sum m v                                          */
+  double angular_momentum[3]; /* L = sum m x cross v (about the origin)               */
+  double com[3];              /* sum m x / M (0 when M <= 0)                          */
+  int32_t n;                  /* bodies                                               */
+  int32_t reserved[7];
+} bh_energy_stats;
+/* Builds the tree of the current positions on the context's stream as bh_step would (bbox, keys, sort, build, COM
+   digests), walks it for accelerations and potentials, reduces, and SYNCHRONISES.  BH_ERR_DEVICE_FLAG (sums filled in,
+   invalid) when a sticky flag is set, as bh_sync; BH_ERR_BAD_ARG on a domain-decomposed context (bh_dd_init) and above
+   ~26.8M bodies (the fast walk's record addressing).  It does not perturb the run: a run with bh_energy between steps
+   produces bit for bit the states of a run without it.  It overwrites the accelerations (those of the force_variant = 1
+   walk) and leaves the stage bits as bh_bbox .. bh_force would.  The first call allocates 4 bytes per body. */
+int bh_energy(bh_ctx* c, bh_energy_stats* out);
+/* phi of the last bh_energy, n floats in caller order; BH_ERR_ORDER before the first bh_energy after an upload and after
+   anything that moved the bodies since (bh_step, bh_integrate, bh_sort) */
+int bh_download_potential(bh_ctx* c, float* phi);
+
 /* ---- multi-rank plumbing: raw device views (valid until bh_destroy) ---- */
 /* acc is float4[n] (ax,ay,az,unused) in Morton-sorted order; an all-gather of the
    per-rank [lo,hi) slabs straight into this buffer completes the exchange step. */

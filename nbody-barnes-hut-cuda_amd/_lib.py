@@ -53,6 +53,13 @@ class BhWalkStats(C.Structure):
                 ("reserved", C.c_uint64 * 1)]
 
 
+class BhEnergyStats(C.Structure):
+    """struct bh_energy_stats: system sums of bh_energy (fp64)."""
+    _fields_ = [("kinetic", C.c_double), ("potential", C.c_double), ("total", C.c_double), ("mass", C.c_double),
+                ("momentum", C.c_double * 3), ("angular_momentum", C.c_double * 3), ("com", C.c_double * 3),
+                ("n", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class BhDdSizes(C.Structure):
     """struct bh_dd_sizes: buffer sizes of the domain-decomposed stepping."""
     _fields_ = [(k, C.c_int64) for k in
@@ -156,6 +163,8 @@ SYMBOLS = [
     ("bh_get_stats", C.c_int, [_P, C.POINTER(BhStats)]),
     ("bh_set_timing", C.c_int, [_P, C.c_int]),
     ("bh_sync", C.c_int, [_P]),
+    ("bh_energy", C.c_int, [_P, C.POINTER(BhEnergyStats)]),
+    ("bh_download_potential", C.c_int, [_P, _F]),
     ("bh_device_acc", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     ("bh_bind_acc", C.c_int, [_P, _P]),
     ("bh_timing_history", C.c_int, [_P, _F, _F, C.c_int, C.POINTER(C.c_int)]),

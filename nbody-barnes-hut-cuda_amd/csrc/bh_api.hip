@@ -77,6 +77,7 @@ int bh_last_hip_error(const bh_ctx* c) { return c ? c->last_hip : 0; }
 int bh_n(const bh_ctx* c) { return c ? c->n : 0; }
 
 static void drop_graphs(bh_ctx* c);
+static int d2h(bh_ctx* c, void* dst, const void* src, size_t bytes);
 
 static void free_all(bh_ctx* c) {
   if (!c) return;
@@ -90,7 +91,7 @@ static void free_all(bh_ctx* c) {
                   c->sw_ticket, c->sp_keys, c->sp_count, c->bbox_partial, c->bounds_next, c->ibox_rows,
                   c->bounds, c->d8, c->ksamp, c->fuse_rows, c->fuse_cnt, c->pa, c->pb, c->pn,
                   c->cb, c->ttot, c->blk_done, c->rec, c->frec, c->er_lo, c->er_hi, c->P, c->info, c->scan_tmp,
-                  c->cV, c->cO, c->cP};
+                  c->cV, c->cO, c->cP, c->pot, c->en_part, c->en_cnt};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->evring) {
@@ -305,6 +306,7 @@ int bh_upload(bh_ctx* c, const float* x, const float* y, const float* z, const f
   c->slow_seen = 0;       // (the counter itself is cleared with the device info block below)
   c->slow_seen_sorts = c->sort_calls;
   c->bounds_next_ok = false;
+  c->pot_ok = false;
   BH_HIP(c, bhk_pack(c));
   BH_HIP(c, hipMemsetAsync(c->info, 0, sizeof(bh_devinfo), c->stream));  // clears the sticky flags
   BH_HIP(c, hipMemsetAsync(c->acc, 0, N * sizeof(float4), c->stream));
@@ -347,6 +349,7 @@ int bh_morton(bh_ctx* c) {
 int bh_sort(bh_ctx* c) {
   BH_NEED(c, BH_ST_MORTON);
   if (c->stage & BH_ST_SORT) return BH_ERR_ORDER;  // sorting twice would permute twice
+  c->pot_ok = false;  // the potentials are stored in the order the bodies leave
   // the tree of an earlier digest-only step stays downloadable: make its records canonical before the bodies
   // they refer to are reordered (stage calls only; bh_step rebuilds the tree anyway)
   if ((c->ever & BH_ST_BUILD) && c->rec_proto && c->com_digests) BH_HIP(c, bhk_canonical_records(c));
@@ -386,6 +389,7 @@ int bh_force(bh_ctx* c) {
 int bh_integrate(bh_ctx* c) {
   BH_NEED(c, BH_ST_FORCE);
   c->bounds_next_ok = false;
+  c->pot_ok = false;
   // domain-decomposed step: the kernel also folds this rank's min / max, the next step's X1 payload — unless the
   // step's last force pass has done both already (bh_dd_force)
   if (c->dd && c->dd_integrated) {
@@ -570,6 +574,7 @@ static void drop_graphs(bh_ctx* c) {
 // at 65,536: graph kernel nodes are dispatched with more packet overhead than back-to-back stream launches).
 int bh_step(bh_ctx* c) {
   BH_NEED(c, BH_ST_UPLOADED);
+  c->pot_ok = false;
 #ifdef BH_STUDY
   static const bool env_off = getenv("BH_NO_GRAPH") != nullptr;
 #else
@@ -612,6 +617,83 @@ int bh_step(bh_ctx* c) {
   c->stage = BH_ST_UPLOADED;
   c->steps++;
   return BH_OK;
+}
+
+// ---- energy diagnostics ----
+// The tree of the current positions, built as bh_step builds it (same cube, keys, stable sort, build, COM), then the
+// potential walk and the reduction.  What a later bh_step reads is left as that step would find it without this call:
+//   * the cube: a step after a fused integrate takes bounds_next (bounds_next_ok) — this call copies that cube into
+//     bounds and leaves bounds_next / bounds_next_ok alone, so both sort by the same keys; otherwise it runs bbox, as
+//     the step will, on the same positions;
+//   * the order: the sort is stable and its input is the order the step's own sort would have produced from the same
+//     keys, so the step's sort yields the same permutation; `cur`, key_buf, the splitter buffers (sp_par, keys_split)
+//     and sort_calls advance exactly as a step's sort advances them, and no captured step graph depends on them
+//     (graph steps never use the splitter sort; the look-back tags live on the device);
+//   * rec_proto / com_digests: as the step's COM stage leaves them (canonical records for strict / literal contexts);
+//   * steps, the timing ring and the fused-launch counters are not touched: no event is recorded and nothing integrates.
+static int energy_launch(bh_ctx* c) {
+  const size_t N = (size_t)c->n;
+  // first call: 4 bytes per body, the partials and their counters
+  if (!c->pot && dalloc(&c->pot, N) != hipSuccess) return BH_ERR_OOM;
+  if (!c->en_part && dalloc(&c->en_part, (size_t)(BH_ENERGY_BLOCKS + 1) * BH_ENERGY_SUMS) != hipSuccess)
+    return BH_ERR_OOM;
+  if (!c->en_cnt) {
+    if (dalloc(&c->en_cnt, (size_t)64) != hipSuccess) return BH_ERR_OOM;
+    BH_HIP(c, hipMemsetAsync(c->en_cnt, 0, 64 * sizeof(u32), c->stream));
+  }
+  if (c->bounds_next_ok)
+    BH_HIP(c, hipMemcpyAsync(c->bounds, c->bounds_next, 8 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  else
+    BH_HIP(c, bhk_bbox(c));
+  BH_HIP(c, bhk_keys(c));
+  c->key_buf = 0;
+  BH_HIP(c, bhk_sort(c));
+  BH_HIP(c, bhk_build(c, true));
+  BH_HIP(c, bhk_com_records(c, c->p.strict_fp || c->p.literal_force));
+  BH_HIP(c, bhk_force_pot(c, c->pot));
+  BH_HIP(c, bhk_energy_sums(c));
+  c->stage = BH_ST_UPLOADED | BH_ST_BBOX | BH_ST_MORTON | BH_ST_SORT | BH_ST_BUILD | BH_ST_COM | BH_ST_FORCE;
+  c->ever |= c->stage;
+  return BH_OK;
+}
+
+int bh_energy(bh_ctx* c, bh_energy_stats* out) {
+  if (!c || !out) return BH_ERR_BAD_ARG;
+  if (c->dd) return BH_ERR_BAD_ARG;  // a rank holds a part of the system: a group reduction is not implemented
+  if (!(c->stage & BH_ST_UPLOADED)) return BH_ERR_ORDER;
+  // the fast walk addresses the digest pool with 32-bit byte offsets (plan_force: up to ~26.8M bodies)
+  if ((long long)BH_FREC_POOL(c->rec_cap, c->n) >= (1ll << 27)) return BH_ERR_BAD_ARG;
+  memset(out, 0, sizeof(*out));
+  c->pot_ok = false;
+  int s = energy_launch(c);
+  if (s) return s;
+  double h[BH_ENERGY_SUMS];
+  s = d2h(c, h, c->en_part + (size_t)BH_ENERGY_BLOCKS * BH_ENERGY_SUMS, sizeof(h));
+  if (s) return s;
+  s = bh_sync(c);  // BH_ERR_DEVICE_FLAG: the sums are filled in, but invalid
+  if (s != BH_OK && s != BH_ERR_DEVICE_FLAG) return s;
+  c->pot_ok = s == BH_OK;
+  const double M = h[0];
+  out->n = c->n;
+  out->mass = M;
+  out->kinetic = 0.5 * h[1];
+  out->potential = 0.5 * h[2];
+  out->total = out->kinetic + out->potential;
+  for (int k = 0; k < 3; k++) {
+    out->momentum[k] = h[3 + k];
+    out->angular_momentum[k] = h[6 + k];
+    out->com[k] = M > 0.0 ? h[9 + k] / M : 0.0;
+  }
+  return s;
+}
+
+int bh_download_potential(bh_ctx* c, float* phi) {
+  if (!c || !phi) return BH_ERR_BAD_ARG;
+  if (!c->pot_ok) return BH_ERR_ORDER;
+  BH_HIP(c, bhk_unpack_pot(c));
+  int s = d2h(c, phi, c->stage_buf, (size_t)c->n * sizeof(float));
+  if (s) return s;
+  return sync_raw(c);
 }
 
 // ---- downloads ----

@@ -336,11 +336,14 @@ __device__ __forceinline__ void load_frec2(cfloat_t* base, int e, FRec& a, FRec&
     const u64 opnm = __builtin_amdgcn_ballot_w64((R).thr2 >= d2);                        \
     const u64 takem = mask & ~opnm, openm = mask & opnm;                                 \
     const float rinv = __builtin_amdgcn_rsqf(d2);                                        \
-    const float f = ((R).gm * rinv) * (rinv * rinv);                                     \
-    const float fm = __builtin_amdgcn_inverse_ballot_w64(takem) ? f : 0.0f;              \
+    const float grinv = (R).gm * rinv;                                                   \
+    const float f = grinv * (rinv * rinv);                                               \
+    const bool take = __builtin_amdgcn_inverse_ballot_w64(takem);                        \
+    const float fm = take ? f : 0.0f;                                                    \
     ax = fmaf(fm, dx, ax);                                                               \
     ay = fmaf(fm, dy, ay);                                                               \
     az = fmaf(fm, dz, az);                                                               \
+    if (POT) phi -= take ? grinv : 0.0f; /* potential: -G m / sqrt(d2 + eps2) */         \
     if (openm != 0ull) {                                                                 \
       {                                                                                  \
         if (sp < 64 * SETS) {                                                            \
@@ -354,11 +357,12 @@ __device__ __forceinline__ void load_frec2(cfloat_t* base, int e, FRec& a, FRec&
   }
 
 // One wave's traversal from record `root` for the lanes of m0; returns false if the cross-lane stack
-// (64 * SETS entries) overflowed, in which case ax..az are incomplete.
-template <int SETS, bool BUDGET>
+// (64 * SETS entries) overflowed, in which case ax..az are incomplete.  POT (bh_energy): also subtract G m rinv of every
+// record the lane takes from phi — the same records, the same rinv; the POT = false instances are unchanged code.
+template <int SETS, bool BUDGET, bool POT = false>
 __device__ __forceinline__ bool fast_traverse(cfloat_t* frec, int root, u64 m0, float px, float py, float pz,
                                               float eps2, float& ax, float& ay, float& az, int budget,
-                                              bool& limit_hit) {
+                                              bool& limit_hit, float& phi) {
   WaveStack st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int sp = 0;
   bool overflow = false;
@@ -390,6 +394,13 @@ __device__ __forceinline__ bool fast_traverse(cfloat_t* frec, int root, u64 m0, 
     } while (k0 < count);
   }
   return !overflow;
+}
+template <int SETS, bool BUDGET>
+__device__ __forceinline__ bool fast_traverse(cfloat_t* frec, int root, u64 m0, float px, float py, float pz,
+                                              float eps2, float& ax, float& ay, float& az, int budget,
+                                              bool& limit_hit) {
+  float phi = 0.0f;
+  return fast_traverse<SETS, BUDGET, false>(frec, root, m0, px, py, pz, eps2, ax, ay, az, budget, limit_hit, phi);
 }
 
 // ------------------------------------------------------------------ hand-scheduled traversal
@@ -1006,6 +1017,39 @@ __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_fast_kernel(const flo
   if (!FUSE) return;
 
   fuse_integrate_and_fold(fz, chunk * (int)(blockDim.x >> 6) + wib, i, valid, lane, px, py, pz, pm, ax, ay, az);
+}
+
+// bh_energy: the walk of force_fast_kernel<1, false> (force_variant = 1, one wave per group) that also sums every body's
+// potential (fast_traverse POT).  Same records, same order, same arithmetic: the accelerations are those of that launch
+// bit for bit.  The walk meets the body's own record (or takes an accepted cell that holds the body); its own term,
+// -G m / eps, is added back once at the end with the arithmetic of a walk term (d2 = eps2 exactly for dx = dy = dz = 0).
+// Outside a decomposed pass the walk has no traversal budget, so BH_FLAG_TRAVERSAL_LIMIT cannot arise here.
+__global__ __launch_bounds__(256) BH_WALK_SGPRS void force_pot_kernel(const float* __restrict__ frec_g,
+                                                                      const float4* posm, float4* __restrict__ acc,
+                                                                      float* __restrict__ pot, int n, float G,
+                                                                      float eps2, int xcd_mode,
+                                                                      bh_devinfo* __restrict__ info, int group) {
+  cfloat_t* frec = (cfloat_t*)frec_g;
+  const int lane = threadIdx.x & 63;
+  const int wib = threadIdx.x >> 6;
+  const int chunk = block_chunk(xcd_mode);
+  const int i = (chunk * (int)(blockDim.x >> 6) + wib) * group + lane;
+  const bool valid = lane < group && i < n;
+  const float4 p = valid ? posm[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float ax = 0.0f, ay = 0.0f, az = 0.0f, phi = 0.0f;
+  const u64 m0 = __builtin_amdgcn_ballot_w64(valid);
+  if (m0 == 0) return;
+  bool limit = false;
+  if (!fast_traverse<1, false, true>(frec, 0, m0, p.x, p.y, p.z, eps2, ax, ay, az, 0, limit, phi)) {
+    ax = ay = az = phi = 0.0f;
+    if (lane == 0) atomicAdd(&info->redo_waves, 1);
+    if (!fast_traverse<3, false, true>(frec, 0, m0, p.x, p.y, p.z, eps2, ax, ay, az, 0, limit, phi) && lane == 0)
+      atomicOr(&info->flags, BH_FLAG_STACK_OVERFLOW);
+  }
+  if (!valid) return;
+  const float gm = p.w > 0.0f ? G * p.w : 0.0f;  // the body's digest (com_kernel)
+  acc[i] = make_float4(ax, ay, az, 0.0f);
+  pot[i] = phi + gm * __builtin_amdgcn_rsqf(eps2);
 }
 
 // ------------------------------------------------------------------ cooperative walk (K waves per group)
@@ -1764,6 +1808,19 @@ hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t strea
   return force_launch(c, p, stream, acc, root, fz_on ? &fz : nullptr, hold, nullptr);
 }
 
+
+// bh_energy: accelerations and potentials of all bodies (force_pot_kernel), bodies per wave as the force_variant = 1
+// launch takes them (the one-wave walk's results do not depend on it)
+hipError_t bhk_force_pot(bh_ctx* c, float* pot) {
+  const int n = c->n;
+  const int group = n <= 20 * 1024 ? 16 : (n <= 56 * 1024 ? 32 : 64);
+  const int xcd = resolve_xcd_mode(c, n, group);
+  const int block = BH_FORCE_BLOCK_DEFAULT;
+  const int waves = (n + group - 1) / group;
+  force_pot_kernel<<<xcd_grid(xcd, kXcdRun, (waves * 64 + block - 1) / block), block, 0, c->stream>>>(
+      (const float*)c->frec, c->posm[c->cur], c->acc, pot, n, c->p.G, c->p.eps2, xcd, c->info, group);
+  return hipGetLastError();
+}
 
 hipError_t bhk_pack(bh_ctx* c) {
   const int n = c->n;

@@ -195,6 +195,12 @@ struct bh_ctx {
   int g_keybuf[2];
   bool graph_failed;
 
+  // energy diagnostics (bh_energy, bh_energy.hip): allocated by the first call, null until then
+  float* pot;         // [n] potential of every body, sorted order (force_pot_kernel)
+  double* en_part;    // [BH_ENERGY_BLOCKS][BH_ENERGY_SUMS] per-block fp64 sums, then [BH_ENERGY_SUMS] totals
+  u32* en_cnt;        // bh_last_block counters of the reduction (left at zero)
+  bool pot_ok;        // pot holds the potentials of the bodies as they are now (cleared by whatever moves them)
+
   // timing
   bool timing;
   int timing_mode;  // 1: event after every stage; 2: only the pair around the force launch
@@ -310,6 +316,12 @@ int bhk_force_walk_rows(const bh_ctx* c);               // waves (rows) of that 
 #define BH_WALK_ROW 16                                  // u32 words per row
 hipError_t bhk_force_trace(bh_ctx* c, u32* trace, int cap_rows, int* rows);  // measurement: one row per wave
 hipError_t bhk_integrate(bh_ctx* c, bool with_bbox);
+// bh_energy (bh_energy.hip, bh_force.hip)
+#define BH_ENERGY_BLOCKS 1024  // most workgroups of the reduction (fewer for small n: one per 256 bodies)
+#define BH_ENERGY_SUMS 12      // sum m, m |v|^2, m phi, m v (3), m x cross v (3), m x (3)
+hipError_t bhk_force_pot(bh_ctx* c, float* pot);  // the force_variant = 1 walk + potentials, into c->acc and pot
+hipError_t bhk_energy_sums(bh_ctx* c);             // c->en_part + BH_ENERGY_BLOCKS * BH_ENERGY_SUMS <- the 12 sums
+hipError_t bhk_unpack_pot(bh_ctx* c);              // stage_buf[0, n) <- pot in caller order
 void bh_dd_free(bh_ctx* c);  // bh_dd.hip
 // measurement (bh_rank_replay_force_phase, bh_group.hip): the force phase of the last completed step run again
 extern "C" int bh_dd_replay_begin(bh_ctx* c, int split, int split_pct, int saved[4]);

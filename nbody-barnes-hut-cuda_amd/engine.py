@@ -182,6 +182,22 @@ class Engine:
     def sync(self):
         self._ck(lib.bh_sync(self._h), "bh_sync")
 
+    def energy(self):
+        """-> dict of the current state's system sums (bh_energy, fp64): kinetic K, potential W, total E = K + W, mass,
+        momentum, angular_momentum (about the origin), com.  Builds the tree of the current positions and walks it
+        (accelerations overwritten, the run itself unperturbed); synchronises."""
+        st = _lib.BhEnergyStats()
+        self._ck(lib.bh_energy(self._h, C.byref(st)), "bh_energy")
+        return dict(kinetic=st.kinetic, potential=st.potential, total=st.total, mass=st.mass,
+                    momentum=tuple(st.momentum), angular_momentum=tuple(st.angular_momentum), com=tuple(st.com),
+                    n=st.n)
+
+    def download_potential(self):
+        """-> float32[n]: every body's potential from the last energy() call, caller order"""
+        phi = np.empty(self.n, dtype=np.float32)
+        self._ck(lib.bh_download_potential(self._h, phi.ctypes.data_as(_F)), "bh_download_potential")
+        return phi
+
     def set_timing(self, on=True):
         """True / 1: events after every stage of a step; 2: only around the force launch (cheap); 3: that pair on
         every 4th step; False: off"""

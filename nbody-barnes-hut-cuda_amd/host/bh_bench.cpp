@@ -19,6 +19,9 @@
 //                                beside X4, then the remote pass), one pass after X4 (the default), or whichever the
 //                                measured X4 makes cheaper (bh_rank_opts.split 2)
 //            [--split-pct P]     per cent of a rank's bodies whose walk is split (default 30)
+//            [--energy K]        every K frames, outside the timed region: one line with the step, the kinetic
+//                                energy K, W, E and (E - E0) / |E0| (bh_energy; E0 = before the first frame);
+//                                single context only
 //            [--replay | --replay-rank Q]  after the run (Q: that rank only): every rank's force phase of the last step run again on its own
 //                                streams with nothing else on the GPU, one pass / 20 / 30 / 100 % split, an idle
 //                                wave of 0 / 125 / 250 us in the place of X4 (one-GPU rehearsals: what a rank-step
@@ -140,6 +143,7 @@ int main(int argc, char** argv) {
   int replay_rank = -1;
   std::vector<int> devs;
   int frames = 1000;  // ref:353
+  int energy_every = 0;
   int warmup = 0;
   int device = 0;
   bool plummer = false, msvc = false, quiet = false;
@@ -173,6 +177,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--replay")) replay = true;
     else if (arg("--replay-rank")) { replay = true; replay_rank = atoi(argv[++i]); }
     else if (arg("--split-pct")) split_pct = atoi(argv[++i]);
+    else if (arg("--energy")) energy_every = atoi(argv[++i]);
     else if (arg("--dump")) dump_path = argv[++i];
     else if (arg("--snapshot")) snap_path = argv[++i];
     else if (!strcmp(argv[i], "--literal-force")) p.literal_force = 1;  // what the CUDA binary computes (D1)
@@ -194,6 +199,10 @@ int main(int argc, char** argv) {
     CK(bh_ic_disc(N, seed, p.G, x.data(), y.data(), z.data(), vx.data(), vy.data(), vz.data(), m.data()));
 
   if (!devs.empty() || gpus > 1 || dist) {
+    if (energy_every > 0) {
+      fprintf(stderr, "--energy needs a single context (bh_energy is not defined for the multi-GPU step)\n");
+      return 2;
+    }
     if (devs.empty())
       for (int q = 0; q < (gpus > 0 ? gpus : 1); q++) devs.push_back(device + q);
     std::vector<float> a[7] = {x, y, z, vx, vy, vz, m};
@@ -216,6 +225,12 @@ int main(int argc, char** argv) {
   double sum = 0.0, sum_force = 0.0;
   int force_samples = 0;
   bh_stats st;
+  bh_energy_stats es;
+  double e0 = 0.0;
+  if (energy_every > 0) {  // does not perturb the run: the frames step exactly as without it
+    CK(bh_energy(c, &es));
+    e0 = es.total;
+  }
   for (int frame = 0; frame < frames; frame++) {
     const double t0 = now_ms();
     CK(bh_step(c));
@@ -228,6 +243,11 @@ int main(int argc, char** argv) {
       force_samples++;
     }
     if (!quiet) printf("%-10d | %-15.3f | %-10.1f\n", frame, ms, 1000.0 / ms);  // ref:366
+    if (energy_every > 0 && (frame + 1) % energy_every == 0) {
+      CK(bh_energy(c, &es));
+      printf("energy step %d K %.9e W %.9e E %.9e dE/|E0| %.3e\n", st.steps, es.kinetic, es.potential, es.total,
+             e0 != 0.0 ? (es.total - e0) / (e0 < 0.0 ? -e0 : e0) : 0.0);
+    }
   }
   const double avg = sum / (frames > 0 ? frames : 1);
   if (!dump_path && !snap_path) {  // per-stage times of one more step (not part of the frames; skipped when the
