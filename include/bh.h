@@ -282,6 +282,33 @@ int bh_energy(bh_ctx* c, bh_energy_stats* out);
    anything that moved the bodies since (bh_step, bh_integrate, bh_sort) */
 int bh_download_potential(bh_ctx* c, float* phi);
 
+/* ---- multipole order (not in the reference): quadrupole moments, opt-in per context ----
+ * Order 1 (default) is the engine above: every accepted cell is a monopole.  Order 2 also stores, for every tree
+ * record with fp32 centre of mass c, mass m and bodies b, the second moment about that same fp32 point,
+ *   S = sum_b m_b (x_b - c)(x_b - c)^T   (6 components; body records have S = 0),
+ * and a taken record adds, with d = c - p, r^2 = |d|^2 + eps2, q = d^T S d, t = tr S (the exact second-order Taylor
+ * term of the softened kernel; the eps2 part of t matters at eps2 = 50):
+ *   acceleration  a += G [ m d / r^3 - 3 S d / r^5 - 3/2 t d / r^5 + 15/2 q d / r^7 ]
+ *   potential     phi += -G [ m / r + 3/2 q / r^5 - 1/2 t / r^3 ]
+ * Nothing else changes: the MAC (d2 + eps2 > (s / theta)^2), records of m <= 0 skipped, unsplit cells opened into
+ * their bodies, bh_energy's self term -G m_i / eps added back once.  Under order 2 every force launch of the context
+ * (bh_step, bh_force, bh_energy) is the compiler-scheduled one-wave walk with these terms, 64 bodies per wave:
+ * force_variant, force_coop and force_group do not apply.  The moments are built in fp64 bottom-up from the children
+ * (no prefix sums) into a separate array allocated by the first switch to order 2 (120 bytes per tree record; contexts
+ * that stay at order 1 allocate nothing).  Snapshots (bh_write_snapshot) do not store the order: set it again after
+ * a restore. */
+/* order 1 or 2; takes effect at the next COM stage (bh_com, bh_step, bh_energy).  A change invalidates the current COM
+   stage: bh_force returns BH_ERR_ORDER until bh_com or bh_step has run again.  BH_ERR_BAD_ARG for any other order,
+   and for order 2 on a context with strict_fp or literal_force set, after bh_dd_init, or above ~26.8M bodies */
+int bh_set_multipole(bh_ctx* c, int order);
+int bh_get_multipole(const bh_ctx* c);
+/* per tree entry, in the order of bh_download_tree: Sxx Syy Szz Sxy Sxz Syz (6 floats per entry, physical units, not
+   scaled by G).  BH_ERR_ORDER unless the current tree's COM stage ran with order 2; BH_ERR_SMALL_BUFFER when
+   capacity < entries (the entry count is still returned; s6 == NULL asks for it alone).  Synchronises. */
+int bh_download_multipoles(bh_ctx* c, float* s6, int capacity, int* n_entries);
+/* Under order 2, bh_force_range, bh_force_count, bh_force_walk_stats and bh_force_launch_trace return BH_ERR_BAD_ARG
+   (they have no quadrupole walk; nothing falls back to monopoles), and so does bh_dd_init. */
+
 /* ---- multi-rank plumbing: raw device views (valid until bh_destroy) ---- */
 /* acc is float4[n] (ax,ay,az,unused) in Morton-sorted order; an all-gather of the
    per-rank [lo,hi) slabs straight into this buffer completes the exchange step. */

@@ -165,6 +165,9 @@ SYMBOLS = [
     ("bh_sync", C.c_int, [_P]),
     ("bh_energy", C.c_int, [_P, C.POINTER(BhEnergyStats)]),
     ("bh_download_potential", C.c_int, [_P, _F]),
+    ("bh_set_multipole", C.c_int, [_P, C.c_int]),
+    ("bh_get_multipole", C.c_int, [_P]),
+    ("bh_download_multipoles", C.c_int, [_P, _F, C.c_int, C.POINTER(C.c_int)]),
     ("bh_device_acc", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     ("bh_bind_acc", C.c_int, [_P, _P]),
     ("bh_timing_history", C.c_int, [_P, _F, _F, C.c_int, C.POINTER(C.c_int)]),

@@ -91,7 +91,7 @@ static void free_all(bh_ctx* c) {
                   c->sw_ticket, c->sp_keys, c->sp_count, c->bbox_partial, c->bounds_next, c->ibox_rows,
                   c->bounds, c->d8, c->ksamp, c->fuse_rows, c->fuse_cnt, c->pa, c->pb, c->pn,
                   c->cb, c->ttot, c->blk_done, c->rec, c->frec, c->er_lo, c->er_hi, c->P, c->info, c->scan_tmp,
-                  c->cV, c->cO, c->cP, c->pot, c->en_part, c->en_cnt};
+                  c->cV, c->cO, c->cP, c->pot, c->en_part, c->en_cnt, c->mom, c->mtmp, c->mparent, c->mcnt};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->evring) {
@@ -131,6 +131,7 @@ int bh_create_on_stream(bh_ctx** out, int n, const bh_params* pin, int device, v
   c->B = p.key_bits / 3;
   c->D = p.max_depth < c->B ? p.max_depth : c->B;
   c->cap = p.leaf_cap;
+  c->multipole = 1;
   c->device = device;
   c->num_cus = 256;
   {
@@ -373,7 +374,7 @@ int bh_com(bh_ctx* c) {
   c->ever |= BH_ST_COM;
   return BH_OK;
 }
-int bh_force_range(bh_ctx* c, int lo, int hi) {
+static int force_range(bh_ctx* c, int lo, int hi) {
   BH_NEED(c, BH_ST_COM);
   if (lo < 0 || hi > c->n || lo > hi) return BH_ERR_BAD_ARG;
   if (!bhk_force_range_aligned(c, lo)) return BH_ERR_BAD_ARG;  // cooperative walk: slabs start on group boundaries
@@ -382,9 +383,13 @@ int bh_force_range(bh_ctx* c, int lo, int hi) {
   c->ever |= BH_ST_FORCE;
   return BH_OK;
 }
+int bh_force_range(bh_ctx* c, int lo, int hi) {
+  if (c && c->multipole == 2) return BH_ERR_BAD_ARG;  // order 2: the whole launch only (bh_force)
+  return force_range(c, lo, hi);
+}
 int bh_force(bh_ctx* c) {
   if (!c) return BH_ERR_BAD_ARG;
-  return bh_force_range(c, 0, c->n);
+  return force_range(c, 0, c->n);
 }
 int bh_integrate(bh_ctx* c) {
   BH_NEED(c, BH_ST_FORCE);
@@ -405,7 +410,7 @@ int bh_integrate(bh_ctx* c) {
 int bh_force_walk_stats(bh_ctx* c, bh_walk_stats* out) {
   if (!out) return BH_ERR_BAD_ARG;
   BH_NEED(c, BH_ST_COM);
-  if (c->p.strict_fp || c->p.literal_force || c->dd) return BH_ERR_BAD_ARG;  // the default walk only
+  if (c->p.strict_fp || c->p.literal_force || c->dd || c->multipole == 2) return BH_ERR_BAD_ARG;  // the default walk only
   return bh_walk_stats_from(c, 0, out);
 }
 
@@ -458,6 +463,7 @@ extern "C" {
 int bh_force_launch_trace(bh_ctx* c, uint32_t* rows, int capacity_rows, int* n_rows) {
   if (!rows || !n_rows || capacity_rows < 1) return BH_ERR_BAD_ARG;
   BH_NEED(c, BH_ST_COM);
+  if (c->multipole == 2) return BH_ERR_BAD_ARG;  // no traced instance of the quadrupole walk
   *n_rows = 0;
   u32* dev = nullptr;
   BH_HIP(c, hipMalloc((void**)&dev, (size_t)capacity_rows * 16));
@@ -481,6 +487,7 @@ int bh_force_launch_trace(bh_ctx* c, uint32_t* rows, int capacity_rows, int* n_r
 
 int bh_force_count(bh_ctx* c) {
   BH_NEED(c, BH_ST_COM);
+  if (c->multipole == 2) return BH_ERR_BAD_ARG;  // the counting walk has no quadrupole terms
   const size_t N = (size_t)c->n;
   BH_HIP(c, bhk_force(c, 0, c->n, true));
   c->stage |= BH_ST_FORCE;
@@ -614,8 +621,63 @@ int bh_step(bh_ctx* c) {
   // replay does not run on the host): proto records again unless the engine keeps canonical ones, digests of THIS tree
   c->rec_proto = !(c->p.strict_fp || c->p.literal_force);
   c->com_digests = true;
+  c->mp_com = c->multipole;  // (bh_set_multipole drops the graphs: they were captured with this order)
   c->stage = BH_ST_UPLOADED;
   c->steps++;
+  return BH_OK;
+}
+
+// ---- multipole order (order 2: quadrupole moments, bh_set_multipole in bh.h) ----
+int bh_set_multipole(bh_ctx* c, int order) {
+  if (!c || (order != 1 && order != 2)) return BH_ERR_BAD_ARG;
+  if (order == 2) {
+    // the quadrupole walk is the compiler-scheduled fast walk: not for the strict / literal arithmetic, not for the
+    // decomposed step, and only where the fast walk addresses the pool (plan_force: up to ~26.8M bodies)
+    if (c->p.strict_fp || c->p.literal_force || c->dd) return BH_ERR_BAD_ARG;
+    if ((long long)BH_FREC_POOL(c->rec_cap, c->n) >= (1ll << 27)) return BH_ERR_BAD_ARG;
+  }
+  if (order == c->multipole) return BH_OK;
+  BH_HIP(c, hipSetDevice(c->device));
+  if (order == 2) {  // first use: 32 + 80 + 8 bytes per record; each buffer on its own, so that a call after an
+                     // OOM allocates what is still missing instead of finding one buffer and assuming the rest
+    const size_t R = (size_t)c->rec_cap;
+    if (!c->mom && dalloc(&c->mom, R * 8) != hipSuccess) return BH_ERR_OOM;
+    if (!c->mtmp && dalloc(&c->mtmp, R) != hipSuccess) return BH_ERR_OOM;
+    if (!c->mparent && dalloc(&c->mparent, R) != hipSuccess) return BH_ERR_OOM;
+    if (!c->mcnt && dalloc(&c->mcnt, R) != hipSuccess) return BH_ERR_OOM;
+  }
+  BH_HIP(c, hipStreamSynchronize(c->stream));
+  drop_graphs(c);  // captured with the other order's COM stage and walk
+  c->multipole = order;
+  // the current COM stage was made for the other order: the walks need bh_com or bh_step first, and the potentials
+  // of the last bh_energy were walked with the other order
+  c->stage &= ~(BH_ST_COM | BH_ST_FORCE);
+  c->pot_ok = false;
+  return BH_OK;
+}
+
+int bh_get_multipole(const bh_ctx* c) { return c ? c->multipole : BH_ERR_BAD_ARG; }
+
+int bh_download_multipoles(bh_ctx* c, float* s6, int capacity, int* n_entries) {
+  if (!c) return BH_ERR_BAD_ARG;
+  if (c->mp_com != 2 || !c->mtmp) return BH_ERR_ORDER;
+  bh_devinfo hi;
+  BH_HIP(c, hipMemcpyAsync(&hi, c->info, sizeof(hi), hipMemcpyDeviceToHost, c->stream));
+  BH_HIP(c, hipStreamSynchronize(c->stream));
+  if (hi.flags & BH_FLAG_POOL_OVERFLOW) return BH_ERR_POOL_OVERFLOW;
+  const int E = hi.n_entries < c->rec_cap ? hi.n_entries : c->rec_cap;
+  if (n_entries) *n_entries = E;
+  if (!s6) return BH_OK;
+  if (capacity < E) return BH_ERR_SMALL_BUFFER;
+  std::vector<bh_q10> h((size_t)E);
+  BH_HIP(c, hipMemcpyAsync(h.data(), c->mtmp, (size_t)E * sizeof(bh_q10), hipMemcpyDeviceToHost, c->stream));
+  BH_HIP(c, hipStreamSynchronize(c->stream));
+  for (int e = 0; e < E; e++) {
+    const bh_q10& q = h[e];
+    float* o = s6 + (size_t)e * 6;
+    o[0] = (float)q.xx; o[1] = (float)q.yy; o[2] = (float)q.zz;
+    o[3] = (float)q.xy; o[4] = (float)q.xz; o[5] = (float)q.yz;
+  }
   return BH_OK;
 }
 

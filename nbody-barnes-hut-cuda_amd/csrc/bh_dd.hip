@@ -1952,6 +1952,7 @@ int bh_dd_query(int n_cap, int world, int mig_cap, int let_cap, bh_dd_sizes* o) 
 int bh_dd_init(bh_ctx* c, int world, int rank, int64_t n_total, int mig_cap, int let_cap, void* pool,
                int64_t pool_records) {
   if (!c || !pool || rank < 0 || rank >= world || c->dd) return BH_ERR_BAD_ARG;
+  if (c->multipole == 2) return BH_ERR_BAD_ARG;  // LET records carry no second moments
   // (a depth cap leaves unsplit cells of many bodies that remote bodies can open: their child blocks have more than
   // the 8 records dd_validate_kernel accepts from another rank — the bound that keeps a walk over a malformed segment
   // short)

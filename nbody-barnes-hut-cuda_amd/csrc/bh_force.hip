@@ -328,7 +328,30 @@ __device__ __forceinline__ void load_frec2(cfloat_t* base, int e, FRec& a, FRec&
   b.meta = __float_as_int(v[13]);
 }
 
-#define BH_FAST_EVAL(R)                                                                  \
+// QUAD (bh_set_multipole order 2): the second-order term of a taken CELL record e (thr2 >= 0: body, null and massless
+// records have none; the test is on wave-uniform scalars, so bodies pay a scalar branch and nothing else).  The row of
+// e (c->mom: G S, -3/2 G tr S, 1/2 G tr S) comes in with one s_load_dwordx8.  With q = d^T S d, t = tr S, r^2 = d2:
+//   a += G [m d / r^3 - 3 S d / r^5 - 3/2 t d / r^5 + 15/2 q d / r^7],  phi -= G [m / r + 3/2 q / r^5 - 1/2 t / r^3]
+// (the exact second-order Taylor term of the softened kernel): fq = f + (15/2 q / r^2 - 3/2 t) / r^5 multiplies d in
+// the monopole's own three fma, the -3 S d / r^5 part is added to the accumulators first.
+#define BH_QUAD_EVAL(E)                                                                  \
+  {                                                                                      \
+    const float8_t S = *(cfloat8_t*)((cchar_t*)mom + ((u32)(E) << 5));                   \
+    const float sdx = fmaf(S[4], dz, fmaf(S[3], dy, S[0] * dx));                         \
+    const float sdy = fmaf(S[5], dz, fmaf(S[1], dy, S[3] * dx));                         \
+    const float sdz = fmaf(S[2], dz, fmaf(S[5], dy, S[4] * dx));                         \
+    const float q = fmaf(dz, sdz, fmaf(dy, sdy, dx * sdx));                              \
+    const float ri2 = rinv * rinv;                                                       \
+    const float ri5 = (ri2 * ri2) * rinv;                                                \
+    fq = fmaf(fmaf(7.5f * q, ri2, S[6]), ri5, f);                                        \
+    const float c5 = take ? -3.0f * ri5 : 0.0f;                                          \
+    ax = fmaf(c5, sdx, ax);                                                              \
+    ay = fmaf(c5, sdy, ay);                                                              \
+    az = fmaf(c5, sdz, az);                                                              \
+    if (POT) phi -= take ? fmaf(1.5f * q, ri5, -S[7] * (ri2 * rinv)) : 0.0f;             \
+  }
+
+#define BH_FAST_EVAL(R, E)                                                               \
   {                                                                                      \
     const float dx = (R).x - px, dy = (R).y - py, dz = (R).z - pz;                       \
     const float d2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2)));                     \
@@ -339,7 +362,9 @@ __device__ __forceinline__ void load_frec2(cfloat_t* base, int e, FRec& a, FRec&
     const float grinv = (R).gm * rinv;                                                   \
     const float f = grinv * (rinv * rinv);                                               \
     const bool take = __builtin_amdgcn_inverse_ballot_w64(takem);                        \
-    const float fm = take ? f : 0.0f;                                                    \
+    float fq = f;                                                                        \
+    if (QUAD && takem != 0ull && (R).thr2 >= 0.0f) BH_QUAD_EVAL(E);                     \
+    const float fm = take ? fq : 0.0f;                                                   \
     ax = fmaf(fm, dx, ax);                                                               \
     ay = fmaf(fm, dy, ay);                                                               \
     az = fmaf(fm, dz, az);                                                               \
@@ -359,10 +384,12 @@ __device__ __forceinline__ void load_frec2(cfloat_t* base, int e, FRec& a, FRec&
 // One wave's traversal from record `root` for the lanes of m0; returns false if the cross-lane stack
 // (64 * SETS entries) overflowed, in which case ax..az are incomplete.  POT (bh_energy): also subtract G m rinv of every
 // record the lane takes from phi — the same records, the same rinv; the POT = false instances are unchanged code.
-template <int SETS, bool BUDGET, bool POT = false>
+// QUAD (order 2): the taken cell records also add their quadrupole term (BH_QUAD_EVAL, moments from `mom`); the
+// QUAD = false instances are unchanged code.
+template <int SETS, bool BUDGET, bool POT = false, bool QUAD = false>
 __device__ __forceinline__ bool fast_traverse(cfloat_t* frec, int root, u64 m0, float px, float py, float pz,
                                               float eps2, float& ax, float& ay, float& az, int budget,
-                                              bool& limit_hit, float& phi) {
+                                              bool& limit_hit, float& phi, cfloat_t* mom = nullptr) {
   WaveStack st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int sp = 0;
   bool overflow = false;
@@ -382,12 +409,12 @@ __device__ __forceinline__ bool fast_traverse(cfloat_t* frec, int root, u64 m0, 
       load_frec2(frec, first + k0, r0, r1);
       load_frec2(frec, first + k0 + 2, r2, r3);
       const int nk = count - k0;
-      BH_FAST_EVAL(r0);
+      BH_FAST_EVAL(r0, first + k0);
       if (nk > 1) {
-        BH_FAST_EVAL(r1);
+        BH_FAST_EVAL(r1, first + k0 + 1);
         if (nk > 2) {
-          BH_FAST_EVAL(r2);
-          if (nk > 3) BH_FAST_EVAL(r3);
+          BH_FAST_EVAL(r2, first + k0 + 2);
+          if (nk > 3) BH_FAST_EVAL(r3, first + k0 + 3);
         }
       }
       k0 += 4;
@@ -1052,6 +1079,76 @@ __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_pot_kernel(const floa
   pot[i] = phi + gm * __builtin_amdgcn_rsqf(eps2);
 }
 
+// Order 2 (bh_set_multipole): the compiler-scheduled walk with the quadrupole terms (fast_traverse QUAD), one wave per
+// 64-body group, the 192-entry redo as in force_fast_kernel.  plan_force picks it for every launch of an order-2
+// context (force_variant, force_coop and force_group do not apply).  FUSE: bh_step's instance, which integrates its
+// bodies and folds the next cube exactly as force_fast_kernel's FUSE instances do.
+template <bool FUSE>
+__global__ __launch_bounds__(256) BH_WALK_SGPRS void force_quad_kernel(const float* __restrict__ frec_g,
+                                                                       const float* __restrict__ mom_g,
+                                                                       const float4* posm, float4* __restrict__ acc,
+                                                                       int lo, int hi, float eps2, int xcd_mode,
+                                                                       bh_devinfo* __restrict__ info,
+                                                                       bh_fuse_args fz) {
+  cfloat_t* frec = (cfloat_t*)frec_g;
+  cfloat_t* mom = (cfloat_t*)mom_g;
+  const int lane = threadIdx.x & 63;
+  const int w = block_chunk(xcd_mode) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+  const int i = lo + w * 64 + lane;
+  const bool valid = i < hi;
+  float px, py, pz, pm;
+  {
+    const float4 p = valid ? posm[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    px = p.x; py = p.y; pz = p.z; pm = p.w;
+  }
+  float ax = 0.0f, ay = 0.0f, az = 0.0f, phi = 0.0f;
+  const u64 m0 = __builtin_amdgcn_ballot_w64(valid);
+  if (m0 == 0) return;
+  bool limit = false;
+  if (!fast_traverse<1, false, false, true>(frec, 0, m0, px, py, pz, eps2, ax, ay, az, 0, limit, phi, mom)) {
+    ax = ay = az = 0.0f;
+    if (lane == 0) atomicAdd(&info->redo_waves, 1);
+    if (!fast_traverse<3, false, false, true>(frec, 0, m0, px, py, pz, eps2, ax, ay, az, 0, limit, phi, mom) &&
+        lane == 0)
+      atomicOr(&info->flags, BH_FLAG_STACK_OVERFLOW);
+  }
+  if (valid) acc[i] = make_float4(ax, ay, az, 0.0f);
+  if (!FUSE) return;
+  fuse_integrate_and_fold(fz, w, i, valid, lane, px, py, pz, pm, ax, ay, az);
+}
+
+// bh_energy of an order-2 context: force_quad_kernel's walk with the potentials (fast_traverse POT + QUAD); the
+// accelerations are that launch's bit for bit, the self term is added back as force_pot_kernel does
+__global__ __launch_bounds__(256) BH_WALK_SGPRS void force_quad_pot_kernel(const float* __restrict__ frec_g,
+                                                                           const float* __restrict__ mom_g,
+                                                                           const float4* posm,
+                                                                           float4* __restrict__ acc,
+                                                                           float* __restrict__ pot, int n, float G,
+                                                                           float eps2, int xcd_mode,
+                                                                           bh_devinfo* __restrict__ info) {
+  cfloat_t* frec = (cfloat_t*)frec_g;
+  cfloat_t* mom = (cfloat_t*)mom_g;
+  const int lane = threadIdx.x & 63;
+  const int i = (block_chunk(xcd_mode) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)) * 64 + lane;
+  const bool valid = i < n;
+  const float4 p = valid ? posm[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float ax = 0.0f, ay = 0.0f, az = 0.0f, phi = 0.0f;
+  const u64 m0 = __builtin_amdgcn_ballot_w64(valid);
+  if (m0 == 0) return;
+  bool limit = false;
+  if (!fast_traverse<1, false, true, true>(frec, 0, m0, p.x, p.y, p.z, eps2, ax, ay, az, 0, limit, phi, mom)) {
+    ax = ay = az = phi = 0.0f;
+    if (lane == 0) atomicAdd(&info->redo_waves, 1);
+    if (!fast_traverse<3, false, true, true>(frec, 0, m0, p.x, p.y, p.z, eps2, ax, ay, az, 0, limit, phi, mom) &&
+        lane == 0)
+      atomicOr(&info->flags, BH_FLAG_STACK_OVERFLOW);
+  }
+  if (!valid) return;
+  const float gm = p.w > 0.0f ? G * p.w : 0.0f;
+  acc[i] = make_float4(ax, ay, az, 0.0f);
+  pot[i] = phi + gm * __builtin_amdgcn_rsqf(eps2);
+}
+
 // ------------------------------------------------------------------ cooperative walk (K waves per group)
 // What bounds a launch that does not fill the GPU (round 4, tools/force_trace.py): a wave's walk is a chain pop ->
 // fetch -> evaluate that runs at its own pace — ~1,500 cycles per child block, three quarters of them waiting for the
@@ -1573,7 +1670,8 @@ static int xcd_grid(int mode, int run, int wgs) {
 //   literal: force_literal_kernel; strict / generic: force_kernel (source-text / fast arithmetic on the canonical
 //   records); fast / fast_pf / fast_v1: force_fast_kernel, one wave per group (hand-scheduled walk without / with the
 //   scalar-cache prefetch, compiler-scheduled walk); coop: force_coop_kernel; mixed: force_mixed_kernel
-enum class force_walk { none, literal, strict, generic, fast, fast_pf, fast_v1, coop, mixed };
+//   quad: force_quad_kernel, every launch of an order-2 context (bh_set_multipole)
+enum class force_walk { none, literal, strict, generic, fast, fast_pf, fast_v1, coop, mixed, quad };
 enum class force_entry { single, counting, pass };  // bh_step / bh_force_range; bh_force_count; a decomposed pass
 struct force_plan {
   force_walk walk = force_walk::none;
@@ -1627,6 +1725,14 @@ static force_plan plan_force(const bh_ctx* c, int lo, int hi, force_entry e, for
   if (rest) *rest = p;
   p.lo = lo; p.hi = hi;
   if (hi <= lo) return p;
+  if (c->multipole == 2) {  // order 2: the quadrupole walk, one wave per 64-body group, whatever the entry
+    p.walk = force_walk::quad;
+    p.group = 64; p.K = 1; p.bulk = c->n;
+    p.xcd = resolve_xcd_mode(c, hi - lo, 64);
+    p.block = BH_FORCE_BLOCK_DEFAULT;
+    p.grid = xcd_grid(p.xcd, kXcdRun, (p.groups() * 64 + p.block - 1) / p.block);
+    return p;
+  }
   // Groups at the end of a launch that are walked by four waves each (force_mixed_kernel; a launch of fewer groups is
   // cooperative throughout): the short jobs have to refill what the long ones free while they drain — a third of the
   // resident waves' worth of groups, whatever the launch size (same-box sweep at 1M bodies, force ms for 0 / 2,048 /
@@ -1723,6 +1829,11 @@ static hipError_t force_launch(const bh_ctx* c, const force_plan& p, hipStream_t
       k<<<p.grid, p.block, p.lds, s>>>(frec, posm, acc, p.lo, p.hi, e2, p.xcd, c->info, p.group, fz, root, hold);
       break;
     }
+    case force_walk::quad: {
+      auto k = fuse ? force_quad_kernel<true> : force_quad_kernel<false>;
+      k<<<p.grid, p.block, 0, s>>>(frec, (const float*)c->mom, posm, acc, p.lo, p.hi, e2, p.xcd, c->info, fz);
+      break;
+    }
     case force_walk::mixed: {
       auto k = fuse ? (p.budget ? force_mixed_kernel<true, true> : force_mixed_kernel<true>)
                     : (trace ? force_mixed_kernel<false, false, true>
@@ -1752,7 +1863,8 @@ hipError_t bhk_force(bh_ctx* c, int lo, int hi, bool count, bool fuse_integrate,
   if (fused) *fused = false;
   force_plan rest;
   const force_plan p = plan_force(c, lo, hi, count ? force_entry::counting : force_entry::single, &rest);
-  const bool fuse = fuse_integrate && fused && p.hand() && lo == 0 && hi == c->n && p.groups() <= c->fuse_waves;
+  const bool fuse = fuse_integrate && fused && (p.hand() || p.walk == force_walk::quad) && lo == 0 && hi == c->n &&
+                    p.groups() <= c->fuse_waves;
   const bh_fuse_args fz{c->posm[c->cur], c->velid[c->cur], c->p.dt,       c->p.max_speed, c->fuse_rows,
                         c->fuse_rows + (size_t)c->fuse_waves * 6, c->fuse_cnt, c->bounds_next, fuse ? p.groups() : 0};
   if (fuse) *fused = true;
@@ -1813,6 +1925,13 @@ hipError_t bhk_force_root(bh_ctx* c, int lo, int hi, int root, hipStream_t strea
 // launch takes them (the one-wave walk's results do not depend on it)
 hipError_t bhk_force_pot(bh_ctx* c, float* pot) {
   const int n = c->n;
+  if (c->multipole == 2) {  // the bodies per wave and placement of the order-2 force launch (plan_force)
+    const force_plan p = plan_force(c, 0, n, force_entry::single);
+    force_quad_pot_kernel<<<p.grid, p.block, 0, c->stream>>>((const float*)c->frec, (const float*)c->mom,
+                                                             c->posm[c->cur], c->acc, pot, n, c->p.G, c->p.eps2, p.xcd,
+                                                             c->info);
+    return hipGetLastError();
+  }
   const int group = n <= 20 * 1024 ? 16 : (n <= 56 * 1024 ? 32 : 64);
   const int xcd = resolve_xcd_mode(c, n, group);
   const int block = BH_FORCE_BLOCK_DEFAULT;

@@ -67,6 +67,12 @@ struct bh_d4 {  // fp64 prefix-sum element: (sum m, sum m*x, sum m*y, sum m*z)
   double m, x, y, z;
 };
 
+struct bh_q10 {  // fp64 moments of one record about its stored fp32 centre c (bh_tree.hip, moments_up_kernel)
+  double m;            // sum m
+  double dx, dy, dz;   // sum m (x - c): the dipole, ~0 but kept (c is a rounded centre)
+  double xx, yy, zz, xy, xz, yz;  // sum m (x - c)(x - c)^T
+};
+
 // stage bits for order checking
 enum {
   BH_ST_UPLOADED = 1,
@@ -200,6 +206,15 @@ struct bh_ctx {
   double* en_part;    // [BH_ENERGY_BLOCKS][BH_ENERGY_SUMS] per-block fp64 sums, then [BH_ENERGY_SUMS] totals
   u32* en_cnt;        // bh_last_block counters of the reduction (left at zero)
   bool pot_ok;        // pot holds the potentials of the bodies as they are now (cleared by whatever moves them)
+
+  // quadrupole moments (bh_set_multipole): allocated when a context first asks for order 2, null until then
+  int multipole;      // expansion order of the next COM stage and of every force walk: 1 (monopoles) or 2
+  int mp_com;         // order the current tree's COM stage ran with (0: no COM stage on the current tree)
+  float* mom;         // [rec_cap][8] the walk's moments, G-scaled, one 32-byte row per record (a record pair = one
+                      // 64-byte line): Sxx Syy Szz Sxy Sxz Syz, -3/2 tr S, 1/2 tr S about the record's fp32 centre
+  bh_q10* mtmp;       // [rec_cap] fp64 mass, dipole and second moment of every record about its fp32 centre
+  int* mparent;       // [rec_cap] parent record (-1: the root)
+  u32* mcnt;          // [rec_cap] children of a record combined so far (bottom-up pass)
 
   // timing
   bool timing;
@@ -338,5 +353,8 @@ hipError_t bhk_com_records(bh_ctx* c, bool canonical, int* spine_pieces = nullpt
                            // canonical = false: digests only; spine_pieces (digest-only pass of the decomposed step):
                            // also lists the rank's pieces (com_kernel)
 hipError_t bhk_canonical_records(bh_ctx* c);  // proto records -> canonical, after a digest-only COM stage
+// order 2: the second moments of the records the last bhk_com_records call described (c->mom, c->mtmp).
+// use_er: the body ranges are in er_lo / er_hi (a canonical COM stage), else in the records' x / y bits
+hipError_t bhk_moments(bh_ctx* c, bool use_er);
 size_t bhk_scan_tmp_bytes(int n);
 size_t bhk_scan_cnt_offset(int n);

@@ -1318,6 +1318,123 @@ __global__ __launch_bounds__(256) void canon_kernel(bh_node* __restrict__ rec, c
   *reinterpret_cast<float4*>(&rec[e]) = o;
 }
 
+// ------------------------------------------------------------------ second moments (bh_set_multipole order 2)
+// S = sum_b m_b (x_b - c)(x_b - c)^T about the record's STORED fp32 centre c (what the walk expands about).  Not from
+// prefix sums: a difference of fp64 prefix sums of m x x^T loses ~1e-16 (M_total / m_cell) (R_system / s_cell)^2 of a
+// cell's own moment to cancellation (1e-1 for a small cell of a cluster far from the origin).  Instead every record
+// is built bottom-up from its children: the leaves (a body: S = 0; an unsplit cell: a direct fp64 sum over its bodies)
+// start a climb, and the LAST child of a cell to arrive (a counter per cell) combines the cell and climbs on.  Each
+// record keeps (M, D, S) about its own fp32 c, D = sum m (x - c) — the dipole, ~M times the rounding of c, kept rather
+// than dropped — so the shift to the parent's c_p is exact algebra in fp64 (delta = c_k - c_p, exact in fp64):
+//   S_p = sum_k S_k + delta D_k^T + D_k delta^T + M_k delta delta^T,   D_p = sum_k D_k + M_k delta,   M_p = sum_k M_k.
+// The combine reads the children in their block order: the same tree gives the same bits whichever thread climbs.
+// Hand-off between climbing threads: bh_internal.h's fence-free scheme (write-through stores, vmcnt(0), relaxed count;
+// agent-scope loads on the reading side).
+
+// parents of every record and zeroed counters (the climb needs both before any thread starts)
+__global__ __launch_bounds__(256) void moments_link_kernel(const bh_node* __restrict__ rec,
+                                                           const bh_devinfo* __restrict__ info, int rec_cap,
+                                                           int* __restrict__ parent, u32* __restrict__ cnt) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int E = min(info->n_entries, rec_cap);
+  if (e >= E) return;
+  cnt[e] = 0u;
+  if (e == 0) parent[0] = -1;
+  const bh_node r = rec[e];
+  if (r.kind == BH_KIND_INTERNAL)
+    for (int k = 0; k < r.count; k++) parent[r.first + k] = e;
+}
+
+__device__ __forceinline__ void q10_publish(bh_q10* dst, const double (&v)[10]) {
+  double* d = reinterpret_cast<double*>(dst);
+#pragma unroll
+  for (int k = 0; k < 10; k++) __hip_atomic_store(d + k, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void q10_collect(const bh_q10* src, double (&v)[10]) {
+  const double* d = reinterpret_cast<const double*>(src);
+#pragma unroll
+  for (int k = 0; k < 10; k++) v[k] = __hip_atomic_load(d + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// s += a child's (M, D, S) about its own centre, shifted by e = c_child - c_parent (exact in fp64)
+__device__ __forceinline__ void q10_shift_add(double (&s)[10], const double (&w)[10], double ex, double ey, double ez) {
+  const double m = w[0];
+  s[0] += m;
+  s[1] += w[1] + m * ex; s[2] += w[2] + m * ey; s[3] += w[3] + m * ez;
+  s[4] += w[4] + 2.0 * ex * w[1] + m * ex * ex;
+  s[5] += w[5] + 2.0 * ey * w[2] + m * ey * ey;
+  s[6] += w[6] + 2.0 * ez * w[3] + m * ez * ez;
+  s[7] += w[7] + ex * w[2] + ey * w[1] + m * ex * ey;
+  s[8] += w[8] + ex * w[3] + ez * w[1] + m * ex * ez;
+  s[9] += w[9] + ey * w[3] + ez * w[2] + m * ey * ez;
+}
+
+// the walk's row of record e: G S, -3/2 G tr S, 1/2 G tr S (bh_internal.h, bh_ctx::mom)
+__device__ __forceinline__ void mom_put(float* __restrict__ mom, int e, const double (&v)[10], double G) {
+  const double t = v[4] + v[5] + v[6];
+  float4* o = reinterpret_cast<float4*>(mom + (size_t)e * 8);
+  o[0] = make_float4((float)(G * v[4]), (float)(G * v[5]), (float)(G * v[6]), (float)(G * v[7]));
+  o[1] = make_float4((float)(G * v[8]), (float)(G * v[9]), (float)(-1.5 * G * t), (float)(0.5 * G * t));
+}
+
+__global__ __launch_bounds__(256) void moments_up_kernel(const bh_node* __restrict__ rec,
+                                                         const bh_frec* __restrict__ frec,
+                                                         const float4* __restrict__ posm,
+                                                         const int* __restrict__ er_lo, const int* __restrict__ er_hi,
+                                                         int use_er, const bh_devinfo* __restrict__ info, int rec_cap,
+                                                         const int* __restrict__ parent, u32* __restrict__ cnt,
+                                                         bh_q10* __restrict__ tmp, float* __restrict__ mom, float G) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int E = min(info->n_entries, rec_cap);
+  if (e >= E) return;
+  const bh_node r = rec[e];
+  if (r.kind == BH_KIND_INTERNAL) return;  // combined by the last of its children to arrive
+  const double Gd = (double)G;
+  double v[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (r.kind != BH_KIND_PAD) {
+    const int lo = use_er ? er_lo[e] : __float_as_int(r.x), hi = use_er ? er_hi[e] : __float_as_int(r.y);
+    if (r.kind == BH_KIND_BODY) {
+      v[0] = (double)posm[lo].w;  // c is the body itself: D = S = 0
+    } else {                      // unsplit cell: its bodies directly
+      const bh_frec cr = frec_get(frec, e);
+      const double cx = cr.x, cy = cr.y, cz = cr.z;
+      for (int b = lo; b < hi; b++) {
+        const float4 q = posm[b];
+        const double m = q.w, dx = (double)q.x - cx, dy = (double)q.y - cy, dz = (double)q.z - cz;
+        v[0] += m;
+        v[1] += m * dx; v[2] += m * dy; v[3] += m * dz;
+        v[4] += m * dx * dx; v[5] += m * dy * dy; v[6] += m * dz * dz;
+        v[7] += m * dx * dy; v[8] += m * dx * dz; v[9] += m * dy * dz;
+      }
+    }
+  }
+  mom_put(mom, e, v, Gd);
+  q10_publish(tmp + e, v);
+  if (r.kind == BH_KIND_PAD) return;  // nobody's child
+  bh_published();
+  int at = e;
+  for (;;) {
+    const int p = parent[at];
+    if (p < 0) return;
+    const bh_node rp = rec[p];
+    if (__hip_atomic_fetch_add(cnt + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (u32)(rp.count - 1)) return;
+    const bh_frec cp = frec_get(frec, p);
+    const double px = cp.x, py = cp.y, pz = cp.z;
+    double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < rp.count; k++) {
+      const int ch = rp.first + k;
+      double w[10];
+      q10_collect(tmp + ch, w);
+      const bh_frec cc = frec_get(frec, ch);
+      q10_shift_add(s, w, (double)cc.x - px, (double)cc.y - py, (double)cc.z - pz);
+    }
+    mom_put(mom, p, s, Gd);
+    q10_publish(tmp + p, s);
+    bh_published();
+    at = p;
+  }
+}
+
 }  // namespace
 
 hipError_t bhk_bbox(bh_ctx* c) {
@@ -1397,6 +1514,7 @@ hipError_t bhk_build(bh_ctx* c, bool pm_scan) {
 
   c->rec_proto = true;  // records carry their body range in x / y until the (canonical) COM stage has run
   c->com_digests = false;
+  c->mp_com = 0;
   const u64* k = c->keys[c->key_buf];
   // every 2^ss-th key, at most kSampMax of them: bisection seeds of the wide-cell searches
   int ss = 12;
@@ -1470,6 +1588,20 @@ hipError_t bhk_com_records(bh_ctx* c, bool canonical, int* spine_pieces, int* sp
                                                      spine_count, c->n);
   if (canonical) c->rec_proto = false;
   c->com_digests = true;
+  c->mp_com = c->multipole;
+  if (c->multipole == 2) return bhk_moments(c, canonical || !proto);
+  return hipGetLastError();
+}
+
+hipError_t bhk_moments(bh_ctx* c, bool use_er) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // bh_set_multipole switches to order 2 only with all four buffers allocated
+  if (!c->mom || !c->mtmp || !c->mparent || !c->mcnt) return hipErrorInvalidValue;
+  const int blocks = (c->rec_cap + 255) / 256;
+  moments_link_kernel<<<blocks, 256, 0, c->stream>>>(c->rec, c->info, c->rec_cap, c->mparent, c->mcnt);
+  moments_up_kernel<<<blocks, 256, 0, c->stream>>>(c->rec, c->frec, c->posm[c->cur], c->er_lo, c->er_hi, use_er ? 1 : 0,
+                                                   c->info, c->rec_cap, c->mparent, c->mcnt, c->mtmp, c->mom, c->p.G);
   return hipGetLastError();
 }
 

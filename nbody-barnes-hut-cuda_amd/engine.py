@@ -198,6 +198,26 @@ class Engine:
         self._ck(lib.bh_download_potential(self._h, phi.ctypes.data_as(_F)), "bh_download_potential")
         return phi
 
+    def set_multipole(self, order):
+        """1: monopoles (default); 2: quadrupole moments from the next COM stage on (bh_set_multipole).  A change
+        invalidates the current COM stage: force() needs com() or step() first.  Not stored in snapshots."""
+        self._ck(lib.bh_set_multipole(self._h, int(order)), "bh_set_multipole")
+
+    @property
+    def multipole(self):
+        """the context's expansion order, 1 or 2"""
+        return int(lib.bh_get_multipole(self._h))
+
+    def download_multipoles(self):
+        """-> float32[entries, 6]: Sxx Syy Szz Sxy Sxz Syz of every tree entry (download_tree's order) about its
+        fp32 centre of mass, physical units; needs a COM stage run with order 2 on the current tree"""
+        cnt = C.c_int(0)
+        self._ck(lib.bh_download_multipoles(self._h, None, 0, C.byref(cnt)), "bh_download_multipoles")
+        s = np.empty((cnt.value, 6), dtype=np.float32)
+        self._ck(lib.bh_download_multipoles(self._h, s.ctypes.data_as(_F), cnt.value, C.byref(cnt)),
+                 "bh_download_multipoles")
+        return s
+
     def set_timing(self, on=True):
         """True / 1: events after every stage of a step; 2: only around the force launch (cheap); 3: that pair on
         every 4th step; False: off"""

@@ -22,6 +22,7 @@
 //            [--energy K]        every K frames, outside the timed region: one line with the step, the kinetic
 //                                energy K, W, E and (E - E0) / |E0| (bh_energy; E0 = before the first frame);
 //                                single context only
+//            [--multipole 2]     quadrupole moments (bh_set_multipole); one header line says so; single context only
 //            [--replay | --replay-rank Q]  after the run (Q: that rank only): every rank's force phase of the last step run again on its own
 //                                streams with nothing else on the GPU, one pass / 20 / 30 / 100 % split, an idle
 //                                wave of 0 / 125 / 250 us in the place of X4 (one-GPU rehearsals: what a rank-step
@@ -144,6 +145,7 @@ int main(int argc, char** argv) {
   std::vector<int> devs;
   int frames = 1000;  // ref:353
   int energy_every = 0;
+  int multipole = 1;
   int warmup = 0;
   int device = 0;
   bool plummer = false, msvc = false, quiet = false;
@@ -178,6 +180,7 @@ int main(int argc, char** argv) {
     else if (arg("--replay-rank")) { replay = true; replay_rank = atoi(argv[++i]); }
     else if (arg("--split-pct")) split_pct = atoi(argv[++i]);
     else if (arg("--energy")) energy_every = atoi(argv[++i]);
+    else if (arg("--multipole")) multipole = atoi(argv[++i]);
     else if (arg("--dump")) dump_path = argv[++i];
     else if (arg("--snapshot")) snap_path = argv[++i];
     else if (!strcmp(argv[i], "--literal-force")) p.literal_force = 1;  // what the CUDA binary computes (D1)
@@ -187,6 +190,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "unknown argument %s\n", argv[i]);
       return 2;
     }
+  }
+  if (multipole != 1 && multipole != 2) {
+    fprintf(stderr, "--multipole takes 1 or 2\n");
+    return 2;
   }
   printf("Pokretanje Benchmarka za N = %d...\n", N);  // ref:287
 
@@ -203,6 +210,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "--energy needs a single context (bh_energy is not defined for the multi-GPU step)\n");
       return 2;
     }
+    if (multipole != 1) {
+      fprintf(stderr, "--multipole 2 needs a single context (the multi-GPU step has no quadrupole moments)\n");
+      return 2;
+    }
     if (devs.empty())
       for (int q = 0; q < (gpus > 0 ? gpus : 1); q++) devs.push_back(device + q);
     std::vector<float> a[7] = {x, y, z, vx, vy, vz, m};
@@ -213,6 +224,10 @@ int main(int argc, char** argv) {
   bh_ctx* c = nullptr;
   CK(bh_create(&c, N, &p, device));
   CK(bh_upload(c, x.data(), y.data(), z.data(), vx.data(), vy.data(), vz.data(), m.data()));
+  if (multipole == 2) {
+    CK(bh_set_multipole(c, 2));
+    printf("multipole order 2: quadrupole moments, compiler-scheduled walk\n");
+  }
   CK(bh_set_timing(c, 3));  // frames: only the event pair around the force launch, on every 4th step (an event
                             // after every stage costs the stream ~40 us per step); the stage line below comes
                             // from one extra step
