@@ -274,7 +274,8 @@ typedef struct bh_energy_stats {
 /* Builds the tree of the current positions on the context's stream as bh_step would (bbox, keys, sort, build, COM
    digests), walks it for accelerations and potentials, reduces, and SYNCHRONISES.  BH_ERR_DEVICE_FLAG (sums filled in,
    invalid) when a sticky flag is set, as bh_sync; BH_ERR_BAD_ARG on a domain-decomposed context (bh_dd_init) and above
-   ~26.8M bodies (the fast walk's record addressing).  It does not perturb the run: a run with bh_energy between steps
+   ~26.8M bodies (the fast walk's record addressing) — a domain-decomposed run measures with bh_rank_step_energy /
+   bh_step_group_energy instead.  It does not perturb the run: a run with bh_energy between steps
    produces bit for bit the states of a run without it.  It overwrites the accelerations (those of the force_variant = 1
    walk) and leaves the stage bits as bh_bbox .. bh_force would.  The first call allocates 4 bytes per body. */
 int bh_energy(bh_ctx* c, bh_energy_stats* out);
@@ -420,6 +421,11 @@ int bh_dd_phase_let(bh_ctx* c, const void* gathered_x3, void* send_x4, int strid
 int bh_dd_phase_force(bh_ctx* c, const void* gathered_x3, int stride, int32_t* counts, int* fits);
 int bh_dd_phase_end(bh_ctx* c, void* send_x1);
 int bh_dd_download(bh_ctx* c, float* posm, float* velid, float* acc);
+/* phi of this rank's bodies from the last energy step (bh_rank_step_energy), n_loc floats in the local order of
+   bh_dd_download (the bodies keep their rank and slot from the integrate to the next step's migration, so the ids in
+   velid.w still map them after the step).  BH_ERR_ORDER before the first energy step and after any later step.
+   Synchronises. */
+int bh_dd_download_potential(bh_ctx* c, float* phi);
 /* Measurement only: bh_force_walk_stats for a rank of the decomposed step — the counted walk of its bodies over the
    stitched pool as the last step left it; which = 0: the tree of the last (or only) force pass, 1: the own-pieces pass
    (two-pass steps) */
@@ -538,6 +544,28 @@ int bh_rank_upload(bh_rank* r, int n_loc, const float* x, const float* y, const 
                    const float* vy, const float* vz, const float* m, const int32_t* ids);
 /* `steps` steps of the protocol (collective: every rank of the comm calls it with the same count) */
 int bh_rank_step(bh_rank* r, int steps);
+/* Energy diagnostics of the decomposed step.  Exactly bh_rank_step(r, 1) — the same launches, the same bits: a run
+ * with energy steps ends in the states of the run without them (every form but the adaptive one, split 2, whose form
+ * depends on timing) — and, in addition, the system sums of bh_energy_stats for the state THAT STEP STARTS FROM: the
+ * positions, velocities and masses bh_group_download / bh_dd_download return before the call, so the numbers compare
+ * directly with bh_energy on one context holding that state.  Collective, like bh_rank_step; synchronises the rank's
+ * stream before it returns.
+ *   - phi_i is defined as for bh_energy (same MAC, records of mass <= 0 add 0, the own term removed once, every body
+ *     gets one), by ONE walk of the whole stitched tree (local octree + full top tree + imported LET segments — the
+ *     canonical octree of the system) from the top tree's root, with the traversal budget of every decomposed pass:
+ *     phi matches a single context's up to summation order and never depends on split, split_pct or let_mode.  It is
+ *     launched once X4 has fitted (the step waits for the X4 headers on the host before its force launches), ahead
+ *     of everything that integrates.
+ *   - every rank reduces its own bodies in fp64 (the deterministic reduction of bh_energy), the ranks all-gather one
+ *     row each (sums, sticky flags, local-failure status) through the rank's bh_comm on its stream, and every rank
+ *     adds the rows in rank order on the host: every rank returns the same bits, over every transport; out->n is the
+ *     total body count.
+ *   - status: BH_ERR_DEVICE_FLAG on every rank (sums filled in, invalid) when a sticky flag is set on any rank; a
+ *     rank whose energy part failed locally still takes part in the exchange, and every rank then returns that rank's
+ *     status (the first such rank in rank order); BH_ERR_BAD_ARG before any exchange on a scripted rank (every rank
+ *     of such a job is scripted) and when the plan's X2 send buffer holds less than 128 bytes (the row travels there).
+ *   - the first energy step allocates 4 bytes per body of the rank's capacity n_cap. */
+int bh_rank_step_energy(bh_rank* r, bh_energy_stats* out);
 int bh_rank_get_info(bh_rank* r, bh_rank_info* out);
 bh_ctx* bh_rank_ctx(bh_rank* r); /* the rank's context: bh_dd_download, bh_get_stats, bh_sync, bh_dd_get_info */
 int bh_rank_buffers_of(bh_rank* r, bh_rank_buffers* out, bh_rank_plan* plan);
@@ -585,6 +613,13 @@ int bh_step_group(bh_group* g, int steps); /* returns when every rank has enqueu
 int bh_group_sync(bh_group* g);            /* bh_sync of every rank */
 int bh_group_download(bh_group* g, float* x, float* y, float* z, float* vx, float* vy, float* vz); /* caller order */
 int bh_group_download_acc(bh_group* g, float* ax, float* ay, float* az);                           /* caller order */
+/* one step of every rank with the energy measured (bh_rank_step_energy): every rank computes the same sums, *out is
+   rank 0's; error handling as bh_step_group, except that an error every rank got from the energy exchange leaves the
+   transport usable */
+int bh_step_group_energy(bh_group* g, bh_energy_stats* out);
+/* phi of every body from the last energy step, caller order (bh_dd_download_potential of every rank mapped through the
+   ids); BH_ERR_ORDER before the first energy step and after any later step */
+int bh_group_download_potential(bh_group* g, float* phi);
 int bh_group_size(const bh_group* g);
 bh_rank* bh_group_rank(bh_group* g, int rank);
 void bh_destroy_group(bh_group* g);

@@ -194,6 +194,7 @@ SYMBOLS = [
     ("bh_dd_phase_force", C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     ("bh_dd_phase_end", C.c_int, [_P, _P]),
     ("bh_dd_download", C.c_int, [_P, _F, _F, _F]),
+    ("bh_dd_download_potential", C.c_int, [_P, _F]),
     ("bh_dd_get_info", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("bh_dd_walk_stats", C.c_int, [_P, C.c_int, C.POINTER(BhWalkStats)]),
     ("bh_dd_pass_times", C.c_int, [_P, _F]),
@@ -214,6 +215,7 @@ SYMBOLS = [
                                           C.POINTER(BhRankPlan), C.POINTER(BhRankOpts)]),
     ("bh_rank_upload", C.c_int, [_P, C.c_int] + [_F] * 7 + [C.POINTER(C.c_int32)]),
     ("bh_rank_step", C.c_int, [_P, C.c_int]),
+    ("bh_rank_step_energy", C.c_int, [_P, C.POINTER(BhEnergyStats)]),
     ("bh_rank_get_info", C.c_int, [_P, C.POINTER(BhRankInfo)]),
     ("bh_rank_ctx", _P, [_P]),
     ("bh_rank_buffers_of", C.c_int, [_P, C.POINTER(BhRankBuffers), C.POINTER(BhRankPlan)]),
@@ -229,6 +231,8 @@ SYMBOLS = [
     ("bh_group_sync", C.c_int, [_P]),
     ("bh_group_download", C.c_int, [_P] + [_F] * 6),
     ("bh_group_download_acc", C.c_int, [_P] + [_F] * 3),
+    ("bh_step_group_energy", C.c_int, [_P, C.POINTER(BhEnergyStats)]),
+    ("bh_group_download_potential", C.c_int, [_P, _F]),
     ("bh_group_size", C.c_int, [_P]),
     ("bh_group_rank", _P, [_P, C.c_int]),
     ("bh_destroy_group", None, [_P]),

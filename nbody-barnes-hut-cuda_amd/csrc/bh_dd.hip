@@ -144,6 +144,14 @@ struct bh_dd_state {
   int* arrive;     // [64] immigrants per rank of the current round (left at zero by the kernel)
   int absorb_seq;  // sequence number of the last dd_absorb_kernel launch
   int let_seq;     // ... of the last dd_validate_kernel launch (host[70]: the received X4 headers are in host_rows)
+  // energy steps (bh_rank_step_energy): the potential walk over the whole stitched tree and the sums of this rank's
+  // bodies, enqueued by bh_dd_phase_force once X4 has fitted, ahead of every launch that integrates
+  int n_cap;       // body capacity (the context's n at bh_dd_init): what the potentials are sized for
+  bool en_want;    // this step measures (bh_dd_energy_request; cleared by the caller after the step)
+  int en_status;   // what the energy part of the last request returned (BH_OK or a rank-local error)
+  bool pot_ok;     // c->pot holds the potentials of the bodies as they are now, in local order (the last energy step;
+                   // cleared by whatever moves bodies between ranks or slots).  Not c->pot_ok: bh_download_potential
+                   // maps by velid.w, which on a rank is a global id
 };
 
 namespace {
@@ -1982,6 +1990,7 @@ int bh_dd_init(bh_ctx* c, int world, int rank, int64_t n_total, int mig_cap, int
   d->top_base2 = (int)sz.top_base + kTopCap;
   d->top_base3 = (int)sz.top_base + 2 * kTopCap;
   d->split_pct = 100;
+  d->n_cap = n_cap;
   d->seg_base = (int)sz.seg_base;
   size_t fl = (size_t)n_cap;
   if ((size_t)world * mig_cap > fl) fl = (size_t)world * mig_cap;
@@ -2089,6 +2098,7 @@ int bh_dd_upload(bh_ctx* c, int n_loc, const float* x, const float* y, const flo
   BH_HIP(c, hipMemsetAsync(c->dd->drift, 0, 192 * sizeof(int), c->stream));
   c->dd->prev_ok = false;  // (sizes per pair start over: the first X4 moves whole slots)
   c->dd->x4_v = false;
+  c->dd->pot_ok = false;
   BH_HIP(c, hipStreamSynchronize(c->stream));
   c->stage = BH_ST_UPLOADED;
   c->ever = BH_ST_UPLOADED;
@@ -2144,6 +2154,7 @@ int bh_dd_migrate_pack(bh_ctx* c, void* send_x2, int limit) {
                                                    c->posm[c->cur ^ 1], c->velid[c->cur ^ 1], (float4*)send_x2,
                                                    limit);
   BH_HIP(c, hipGetLastError());
+  d->pot_ok = false;  // the bodies leave their slots
   if (c->keys_split) {  // bucket counts of keys that no sort consumed (an earlier round of this step): void them
     BH_HIP(c, hipMemsetAsync(c->sp_count + 256 * (c->sp_par & 1), 0, 256 * sizeof(u32), c->stream));
     c->keys_split = false;
@@ -2405,7 +2416,9 @@ int bh_dd_top(bh_ctx* c, const void* gathered_x3, int stride) {
         (const bh_dd_piece*)gathered_x3, d->rank, d->pool, d->top_base, d->seg_base, stride, c->bounds, c->p.G,
         c->p.theta, d->top_ps + (kTopMax + 1), d->top_a + kTopCap, d->top_b + kTopCap,
         d->top_ci + kTopCap, d->ddi, 2);
-    if (d->own_hi < c->n)  // the bodies beyond own_hi walk the whole stitched tree: every piece real
+    // the bodies beyond own_hi walk the whole stitched tree (every piece real); an energy step's potential walk always
+    // does, so a full two-pass step emits that tree too
+    if (d->own_hi < c->n || d->en_want)
       dd_top_emit_kernel<<<(kTopCap + 255) / 256, 256, 0, c->stream>>>(
           (const bh_dd_piece*)gathered_x3, d->rank, d->pool, d->top_base3, d->seg_base, stride, c->bounds, c->p.G,
           c->p.theta, d->top_ps + (kTopMax + 1), d->top_a + kTopCap, d->top_b + kTopCap,
@@ -2571,6 +2584,33 @@ int bh_dd_phase_let(bh_ctx* c, const void* gathered_x3, void* send_x4, int strid
   return s;
 }
 
+// Energy step: potentials of this rank's bodies by one walk of the whole stitched tree from the full top tree's root —
+// top_base in the one-pass form, top_base3 in the two-pass forms (bh_dd_top emits it on energy steps) — and the fp64
+// sums of this rank's bodies (energy_sums_kernel) into c->en_part.  The buffers are the rank's, sized for n_cap.
+static int dd_energy_launch(bh_ctx* c) {
+  bh_dd_state* d = c->dd;
+  const size_t N = (size_t)d->n_cap;
+  if (!c->pot && hipMalloc((void**)&c->pot, N * sizeof(float)) != hipSuccess) {
+    c->pot = nullptr;
+    return BH_ERR_OOM;
+  }
+  if (!c->en_part &&
+      hipMalloc((void**)&c->en_part, (size_t)(BH_ENERGY_BLOCKS + 1) * BH_ENERGY_SUMS * sizeof(double)) != hipSuccess) {
+    c->en_part = nullptr;
+    return BH_ERR_OOM;
+  }
+  if (!c->en_cnt) {
+    if (hipMalloc((void**)&c->en_cnt, 64 * sizeof(u32)) != hipSuccess) {
+      c->en_cnt = nullptr;
+      return BH_ERR_OOM;
+    }
+    BH_HIP(c, hipMemsetAsync(c->en_cnt, 0, 64 * sizeof(u32), c->stream));
+  }
+  BH_HIP(c, bhk_dd_pot(c, d->split ? d->top_base3 : d->top_base, c->pot));
+  BH_HIP(c, bhk_energy_sums(c));
+  return BH_OK;
+}
+
 // The fit of every rank's LET is looked at BEFORE the last force pass is launched (the headers of the received
 // segments are on the host as soon as X4 has arrived: the wait is hidden behind the own-pieces pass): a step whose X4
 // has to be repeated larger launches nothing, and a pass that will not be repeated may integrate (dd_force_impl).
@@ -2588,12 +2628,26 @@ int bh_dd_phase_force(bh_ctx* c, const void* gathered_x3, int stride, int32_t* c
   // slower than the streaming kernel does — 0.100 against 0.055 + 0.021 ms at 1M bodies; one pass integrates as
   // bh_step's launch does)
   const int stage0 = c->stage;
-  s = dd_force_impl(c, !c->dd->replay && (c->dd->world > 1 || !c->dd->split));
-  if (s) return s;
+  const bool allow_fuse = !c->dd->replay && (c->dd->world > 1 || !c->dd->split);
+  // Energy step (bh_dd_energy_request): nothing is enqueued before the host has seen that X4 fits — one host wait on a
+  // rare step — and then the potential walk and the sums go first on the main stream, ahead of the event the remote
+  // pass of a partial two-pass step waits for and of every launch that integrates the bodies.  The force launches that
+  // follow are those of a plain step: the run's bits do not change.
+  const bool energy = c->dd->en_want && !c->dd->replay;
+  if (!energy) {
+    s = dd_force_impl(c, allow_fuse);
+    if (s) return s;
+  }
   s = bh_dd_let_check(c, stride, counts);
   bool left = false;
   if (s == BH_OK || s == BH_ERR_SMALL_BUFFER)
     for (int q = 0; q < c->dd->world; q++) left = left || counts[q] < 0;
+  if (energy && s == BH_OK && !left) {
+    c->dd->en_status = dd_energy_launch(c);  // a local failure here is reported by the energy exchange, the step goes on
+    c->dd->pot_ok = c->dd->en_status == BH_OK;
+    const int sf = dd_force_impl(c, allow_fuse);
+    if (sf) return sf;
+  }
   if (s != BH_OK || left) {  // the launches held themselves back: nothing was walked, nothing integrated
     c->dd_integrated = false;
     c->stage = stage0;
@@ -2744,6 +2798,23 @@ int bh_dd_idle_wave(bh_ctx* c, int us) {
   if (!c || us < 0) return BH_ERR_BAD_ARG;
   if (us > 0) dd_sleep_kernel<<<1, 64, 0, c->stream>>>(100ll * us);
   BH_HIP(c, hipGetLastError());
+  return BH_OK;
+}
+
+int bh_dd_energy_request(bh_ctx* c, int on) {
+  if (!c || !c->dd) return BH_ERR_BAD_ARG;
+  c->dd->en_want = on != 0;
+  if (on) c->dd->en_status = BH_ERR_ORDER;  // (until bh_dd_phase_force has run the energy part)
+  return BH_OK;
+}
+int bh_dd_energy_status(bh_ctx* c) { return (c && c->dd) ? c->dd->en_status : BH_ERR_BAD_ARG; }
+
+int bh_dd_download_potential(bh_ctx* c, float* phi) {
+  if (!c || !c->dd || !phi) return BH_ERR_BAD_ARG;
+  if (!c->dd->pot_ok || !c->pot) return BH_ERR_ORDER;
+  if (c->n > 0)
+    BH_HIP(c, hipMemcpyAsync(phi, c->pot, (size_t)c->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  BH_HIP(c, hipStreamSynchronize(c->stream));
   return BH_OK;
 }
 

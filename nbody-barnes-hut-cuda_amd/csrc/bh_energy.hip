@@ -82,12 +82,30 @@ __global__ __launch_bounds__(256) void unpack_f32_kernel(const float* __restrict
   s[__float_as_int(velid[i].w)] = a[i];
 }
 
+// bh_rank_step_energy: this rank's row of the energy all-gather (BH_ENERGY_ROW doubles) — its sums (zero when sums is
+// null: the energy part failed before them), its sticky flags, its local-failure status, its body count
+__global__ void energy_row_kernel(const double* __restrict__ sums, const bh_devinfo* __restrict__ info, int fail,
+                                  int n, double* __restrict__ row) {
+  const int t = threadIdx.x;
+  if (t >= BH_ENERGY_ROW) return;
+  double v = 0.0;
+  if (t < BH_ENERGY_SUMS)
+    v = sums ? sums[t] : 0.0;
+  else if (t == BH_ENERGY_SUMS)
+    v = (double)info->flags;
+  else if (t == BH_ENERGY_SUMS + 1)
+    v = (double)fail;
+  else if (t == BH_ENERGY_SUMS + 2)
+    v = (double)n;
+  row[t] = v;
+}
+
 }  // namespace
 
 hipError_t bhk_energy_sums(bh_ctx* c) {
   const int n = c->n;
   const int per = (n + kThreads - 1) / kThreads;
-  const int blocks = per < BH_ENERGY_BLOCKS ? per : BH_ENERGY_BLOCKS;
+  const int blocks = per < 1 ? 1 : (per < BH_ENERGY_BLOCKS ? per : BH_ENERGY_BLOCKS);  // (a rank may hold no body)
   energy_sums_kernel<<<blocks, kThreads, 0, c->stream>>>(c->posm[c->cur], c->velid[c->cur], c->pot, n, c->en_part,
                                                         c->en_cnt);
   return hipGetLastError();
@@ -96,5 +114,11 @@ hipError_t bhk_energy_sums(bh_ctx* c) {
 hipError_t bhk_unpack_pot(bh_ctx* c) {
   const int n = c->n;
   unpack_f32_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(c->pot, c->velid[c->cur], n, c->stage_buf);
+  return hipGetLastError();
+}
+
+hipError_t bhk_energy_row(bh_ctx* c, int fail, void* row) {
+  const double* sums = c->en_part ? c->en_part + (size_t)BH_ENERGY_BLOCKS * BH_ENERGY_SUMS : nullptr;
+  energy_row_kernel<<<1, 64, 0, c->stream>>>(fail ? nullptr : sums, c->info, fail, c->n, (double*)row);
   return hipGetLastError();
 }

@@ -1149,6 +1149,38 @@ __global__ __launch_bounds__(256) BH_WALK_SGPRS void force_quad_pot_kernel(const
   pot[i] = phi + gm * __builtin_amdgcn_rsqf(eps2);
 }
 
+// bh_rank_step_energy: the potentials of a rank's bodies over the stitched pool (local tree + top tree + imported LET
+// segments) from the full top tree's root — force_pot_kernel's walk with the traversal budget of every decomposed pass
+// (the LET records come from other ranks), one wave per 64 bodies.  Writes pot only: in the two-pass forms acc and
+// acc2 hold the passes' partial accelerations, which a fused launch adds.  Launched only once the step's X4 has fitted
+// (bh_dd.hip), so it has no hold flag.
+__global__ __launch_bounds__(256) BH_WALK_SGPRS void force_dd_pot_kernel(const float* __restrict__ frec_g,
+                                                                         const float4* posm, float* __restrict__ pot,
+                                                                         int n, float G, float eps2, int xcd_mode,
+                                                                         bh_devinfo* __restrict__ info, int root) {
+  cfloat_t* frec = (cfloat_t*)frec_g;
+  const int lane = threadIdx.x & 63;
+  const int i = (block_chunk(xcd_mode) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6)) * 64 + lane;
+  const bool valid = i < n;
+  const float4 p = valid ? posm[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float ax = 0.0f, ay = 0.0f, az = 0.0f, phi = 0.0f;
+  const u64 m0 = __builtin_amdgcn_ballot_w64(valid);
+  if (m0 == 0) return;
+  bool limit = false;
+  if (!fast_traverse<1, true, true>(frec, root, m0, p.x, p.y, p.z, eps2, ax, ay, az, kTraversalBudget, limit, phi) &&
+      !limit) {
+    ax = ay = az = phi = 0.0f;
+    if (lane == 0) atomicAdd(&info->redo_waves, 1);
+    if (!fast_traverse<3, true, true>(frec, root, m0, p.x, p.y, p.z, eps2, ax, ay, az, kTraversalBudget, limit, phi) &&
+        !limit && lane == 0)
+      atomicOr(&info->flags, BH_FLAG_STACK_OVERFLOW);
+  }
+  if (limit && lane == 0) atomicOr(&info->flags, BH_FLAG_TRAVERSAL_LIMIT);
+  if (!valid) return;
+  const float gm = p.w > 0.0f ? G * p.w : 0.0f;
+  pot[i] = phi + gm * __builtin_amdgcn_rsqf(eps2);
+}
+
 // ------------------------------------------------------------------ cooperative walk (K waves per group)
 // What bounds a launch that does not fill the GPU (round 4, tools/force_trace.py): a wave's walk is a chain pop ->
 // fetch -> evaluate that runs at its own pace — ~1,500 cycles per child block, three quarters of them waiting for the
@@ -1938,6 +1970,18 @@ hipError_t bhk_force_pot(bh_ctx* c, float* pot) {
   const int waves = (n + group - 1) / group;
   force_pot_kernel<<<xcd_grid(xcd, kXcdRun, (waves * 64 + block - 1) / block), block, 0, c->stream>>>(
       (const float*)c->frec, c->posm[c->cur], c->acc, pot, n, c->p.G, c->p.eps2, xcd, c->info, group);
+  return hipGetLastError();
+}
+
+// bh_rank_step_energy: potentials of the rank's bodies from pool record `root` (force_dd_pot_kernel)
+hipError_t bhk_dd_pot(bh_ctx* c, int root, float* pot) {
+  const int n = c->n;
+  if (n < 1) return hipSuccess;
+  const int xcd = resolve_xcd_mode(c, n, 64);
+  const int block = BH_FORCE_BLOCK_DEFAULT;
+  const int waves = (n + 63) / 64;
+  force_dd_pot_kernel<<<xcd_grid(xcd, kXcdRun, (waves * 64 + block - 1) / block), block, 0, c->stream>>>(
+      (const float*)c->frec, c->posm[c->cur], pot, n, c->p.G, c->p.eps2, xcd, c->info, root);
   return hipGetLastError();
 }
 

@@ -273,6 +273,7 @@ struct bh_rank {
   bool x1_ready;
   int32_t let_counts[kMaxWorld];
   int left_rank, left_status;
+  bool en_collective;  // the last energy step's error was decided from the energy exchange (every rank returns it)
   long long steps;
   // profile: one event per phase boundary and profiled step
   bool prof;
@@ -393,7 +394,62 @@ void rank_adapt(bh_rank* r) {
   }
 }
 
-int rank_one_step(bh_rank* r) {
+// Energy exchange of an energy step (bh_rank_step_energy), after phase_end: this rank's row — its fp64 sums, sticky
+// flags, local-failure status and body count — all-gathered through the rank's own transport on its stream, then added
+// in rank order on the host by every rank, so every rank holds the same bits.  The row travels in the X2 buffers, which
+// are free from the end of the migration to the next step's X2 (and are registered with a callback transport).
+int rank_energy_exchange(bh_rank* r, int fail, bh_energy_stats* out) {
+  const bh_comm& c = r->comm;
+  const int P = c.world;
+  const size_t rb = BH_ENERGY_ROW * sizeof(double);
+  if (!fail) fail = bh_dd_energy_status(r->ctx);
+  // a row that cannot be filled on the device still travels (zeros but the failure word, which the host sets below)
+  const bool row_ok = bhk_energy_row(r->ctx, fail, r->buf[X2S]) == hipSuccess;
+  if (!row_ok) {
+    (void)hipGetLastError();
+    fail = fail ? fail : BH_ERR_HIP;
+    double z[BH_ENERGY_ROW] = {};
+    z[BH_ENERGY_SUMS + 1] = (double)fail;
+    (void)hipMemcpyAsync(r->buf[X2S], z, rb, hipMemcpyHostToDevice, r->stream);
+    (void)hipStreamSynchronize(r->stream);
+  }
+  if (c.all_gather(c.user, r->buf[X2R], r->buf[X2S], (int64_t)rb, (void*)r->stream)) return BH_ERR_COMM;
+  std::vector<double> rows((size_t)P * BH_ENERGY_ROW);
+  if (hipMemcpyAsync(rows.data(), r->buf[X2R], (size_t)P * rb, hipMemcpyDeviceToHost, r->stream) != hipSuccess ||
+      hipStreamSynchronize(r->stream) != hipSuccess)
+    return BH_ERR_HIP;
+  double h[BH_ENERGY_SUMS] = {};
+  long long n = 0;
+  int flags = 0, first_fail = 0;
+  for (int q = 0; q < P; q++) {  // rank order, fp64
+    const double* row = rows.data() + (size_t)q * BH_ENERGY_ROW;
+    for (int k = 0; k < BH_ENERGY_SUMS; k++) h[k] += row[k];
+    flags |= (int)row[BH_ENERGY_SUMS];
+    const int f = (int)row[BH_ENERGY_SUMS + 1];
+    if (f && !first_fail) first_fail = f;
+    n += (long long)row[BH_ENERGY_SUMS + 2];
+  }
+  const double M = h[0];
+  out->n = (int32_t)n;
+  out->mass = M;
+  out->kinetic = 0.5 * h[1];
+  out->potential = 0.5 * h[2];
+  out->total = out->kinetic + out->potential;
+  for (int k = 0; k < 3; k++) {
+    out->momentum[k] = h[3 + k];
+    out->angular_momentum[k] = h[6 + k];
+    out->com[k] = M > 0.0 ? h[9 + k] / M : 0.0;
+  }
+  r->en_collective = true;
+  if (first_fail) return first_fail;  // the status of the first rank (in rank order) whose energy part failed
+  if (flags) return BH_ERR_DEVICE_FLAG;  // the sums are filled in, but invalid (as bh_energy)
+  r->en_collective = false;
+  return BH_OK;
+}
+
+// en: an energy step (bh_rank_step_energy) — the engine measures the state the step starts from (bh_dd_phase_force)
+// and the ranks exchange their sums after phase_end, so that the step itself is complete whatever that exchange does
+int rank_one_step(bh_rank* r, bh_energy_stats* en = nullptr) {
   const bh_comm& c = r->comm;
   rank_ops e = r->ops;
   rank_adapt(r);
@@ -562,10 +618,17 @@ int rank_one_step(bh_rank* r) {
   }
   rk_mark(r, 5);
   const int s = e.phase_end(e.user, r->buf[X1S]);  // integrate + the next step's X1 payload
-  if (s) return s;
-  r->x1_ready = true;
-  rk_mark(r, 6);
-  r->steps++;
+  if (s && !en) return s;
+  if (!s) {
+    r->x1_ready = true;
+    rk_mark(r, 6);
+    r->steps++;
+  }
+  if (en) {  // (a rank whose phase_end failed still takes part, with its failure word set: nobody is left waiting)
+    const int se = rank_energy_exchange(r, s, en);
+    if (s) return s;
+    return se;
+  }
   return BH_OK;
 }
 
@@ -909,6 +972,21 @@ int bh_rank_step(bh_rank* r, int steps) {
     if (s) return s;
   }
   return BH_OK;
+}
+
+int bh_rank_step_energy(bh_rank* r, bh_energy_stats* out) {
+  if (!r || !out) return BH_ERR_BAD_ARG;
+  // a scripted rank has no engine to walk; every rank of such a job is scripted, so none enters the step
+  if (!r->ctx || !r->device_mem) return BH_ERR_BAD_ARG;
+  // the row of the energy exchange travels in the X2 buffers (rank_energy_exchange); the plan is the same on every rank
+  if (r->plan.bytes[X2S] < (int64_t)(BH_ENERGY_ROW * sizeof(double))) return BH_ERR_BAD_ARG;
+  if (hipSetDevice(r->device) != hipSuccess) return BH_ERR_NO_DEVICE;
+  memset(out, 0, sizeof(*out));
+  r->en_collective = false;
+  int s = bh_dd_energy_request(r->ctx, 1);
+  if (!s) s = rank_one_step(r, out);
+  (void)bh_dd_energy_request(r->ctx, 0);
+  return s;
 }
 
 int bh_rank_get_info(bh_rank* r, bh_rank_info* o) {
@@ -1318,6 +1396,40 @@ int bh_step_group(bh_group* g, int steps) {
     const int s = bh_rank_step(g->ranks[q], steps);
     if (s && s != BH_ERR_DOMAIN_LEFT) g->abort_transport();  // the other ranks may be waiting for this one
     return s;
+  });
+}
+
+int bh_step_group_energy(bh_group* g, bh_energy_stats* out) {
+  if (!g || !out) return BH_ERR_BAD_ARG;
+  if (g->dead) return BH_ERR_COMM;
+  std::vector<bh_energy_stats> st((size_t)g->P);
+  const int s = g->run_all([g, &st](int q) {
+    bh_rank* r = g->ranks[q];
+    const int s1 = bh_rank_step_energy(r, &st[(size_t)q]);
+    // (an error every rank got from the energy exchange leaves the transport usable: the step is complete everywhere)
+    if (s1 && s1 != BH_ERR_DOMAIN_LEFT && !r->en_collective) g->abort_transport();
+    return s1;
+  });
+  *out = st[0];  // every rank computed the same sums
+  return s;
+}
+
+int bh_group_download_potential(bh_group* g, float* phi) {
+  if (!g || !phi) return BH_ERR_BAD_ARG;
+  return g->run_all([g, phi](int q) {
+    bh_rank* r = g->ranks[q];
+    const size_t k = (size_t)bh_n(r->ctx);
+    std::vector<float> velid(4 * k), pot(k);
+    int s = bh_dd_download_potential(r->ctx, pot.data());
+    if (!s) s = bh_dd_download(r->ctx, nullptr, velid.data(), nullptr);
+    if (s) return s;
+    for (size_t i = 0; i < k; i++) {
+      int32_t id;
+      memcpy(&id, &velid[4 * i + 3], 4);
+      if (id < 0 || id >= g->n_total) return (int)BH_ERR_DEVICE_FLAG;
+      phi[id] = pot[i];
+    }
+    return (int)BH_OK;
   });
 }
 

@@ -337,6 +337,12 @@ hipError_t bhk_integrate(bh_ctx* c, bool with_bbox);
 hipError_t bhk_force_pot(bh_ctx* c, float* pot);  // the force_variant = 1 walk + potentials, into c->acc and pot
 hipError_t bhk_energy_sums(bh_ctx* c);             // c->en_part + BH_ENERGY_BLOCKS * BH_ENERGY_SUMS <- the 12 sums
 hipError_t bhk_unpack_pot(bh_ctx* c);              // stage_buf[0, n) <- pot in caller order
+// bh_rank_step_energy (bh_dd.hip, bh_group.hip)
+#define BH_ENERGY_ROW 16  // doubles per rank in the energy all-gather: the 12 sums, flags, failure status, bodies, 0
+hipError_t bhk_dd_pot(bh_ctx* c, int root, float* pot);  // potentials of a decomposed pass from pool record root
+hipError_t bhk_energy_row(bh_ctx* c, int fail, void* row);  // row[BH_ENERGY_ROW] (device) <- this rank's row
+extern "C" int bh_dd_energy_request(bh_ctx* c, int on);      // the next bh_dd_phase_force measures the energy
+extern "C" int bh_dd_energy_status(bh_ctx* c);               // what the last request's energy part returned
 void bh_dd_free(bh_ctx* c);  // bh_dd.hip
 // measurement (bh_rank_replay_force_phase, bh_group.hip): the force phase of the last completed step run again
 extern "C" int bh_dd_replay_begin(bh_ctx* c, int split, int split_pct, int saved[4]);

@@ -505,6 +505,31 @@ class DomainStepper:
         phase_end  (collective: every rank calls it with the same count)"""
         L = _lib()
         st = L.lib.bh_rank_step(self._h, int(steps))
+        self._raise(st, "bh_rank_step")
+
+    def step_energy(self):
+        """bh_rank_step_energy: ONE step, exactly as step(1), that also measures the system's energy of the state it
+        starts from.  -> the dict of Engine.energy() (kinetic, potential, total, mass, momentum, angular_momentum, com,
+        n: the whole system's), the same bits on every rank.  Collective; synchronises the rank's stream."""
+        L = _lib()
+        e = L.BhEnergyStats()
+        st = L.lib.bh_rank_step_energy(self._h, C.byref(e))
+        self._raise(st, "bh_rank_step_energy")
+        return dict(kinetic=e.kinetic, potential=e.potential, total=e.total, mass=e.mass,
+                    momentum=tuple(e.momentum), angular_momentum=tuple(e.angular_momentum), com=tuple(e.com), n=e.n)
+
+    def download_potential(self):
+        """-> (ids, phi): this rank's bodies' potentials from the last step_energy(), in the order of local_state()"""
+        L = _lib()
+        phi = np.empty(self.e.n, np.float32)
+        st = L.lib.bh_dd_download_potential(L.lib.bh_rank_ctx(self._h), phi.ctypes.data_as(L._F))
+        if st != 0:
+            raise self.pkg.BhError(st, "bh_dd_download_potential")
+        _, _, ids, _ = self.e.dd_download()
+        return ids, phi
+
+    def _raise(self, st, what):
+        L = _lib()
         self._sync_info()
         if st == 0:
             return
@@ -521,7 +546,7 @@ class DomainStepper:
         err = getattr(self.comm, "error", None) or getattr(self, "_script_error", None)
         if err is not None:
             raise err
-        raise self.pkg.BhError(st, "bh_rank_step")
+        raise self.pkg.BhError(st, what)
 
     def local_state(self):
         """(ids, posm[n,4], vel[n,3], acc[n,3]) of this rank's bodies"""

@@ -19,9 +19,13 @@
 //                                beside X4, then the remote pass), one pass after X4 (the default), or whichever the
 //                                measured X4 makes cheaper (bh_rank_opts.split 2)
 //            [--split-pct P]     per cent of a rank's bodies whose walk is split (default 30)
-//            [--energy K]        every K frames, outside the timed region: one line with the step, the kinetic
-//                                energy K, W, E and (E - E0) / |E0| (bh_energy; E0 = before the first frame);
-//                                single context only
+//            [--energy K]        every K frames: one line with the step, the kinetic energy K, W, E and
+//                                (E - E0) / |E0| (E0 = before the first frame).  Single context: bh_energy, outside the
+//                                timed region.  Multi-GPU step: the state after frame f is measured by the step that
+//                                follows it (bh_step_group_energy — a real step, so no step runs twice; the first
+//                                frame's step gives E0, the first step after the frames the last line); those frames
+//                                are timed and printed as usual, and one more line gives how many frames measured and
+//                                the mean of the others
 //            [--multipole 2]     quadrupole moments (bh_set_multipole); one header line says so; single context only
 //            [--replay | --replay-rank Q]  after the run (Q: that rank only): every rank's force phase of the last step run again on its own
 //                                streams with nothing else on the GPU, one pass / 20 / 30 / 100 % split, an idle
@@ -52,7 +56,7 @@ static double now_ms() {
 // the frame loop of main() (ref:353-367) over bh_step_group: every rank steps, then the whole node is synchronised
 static int run_group(int N, int frames, int warmup, bool quiet, const bh_params& p, const std::vector<int>& devs,
                      int split, int split_pct, const char* ic_name, std::vector<float>* a, const char* dump_path, const char* snap_path,
-                     bool replay, int replay_rank) {
+                     bool replay, int replay_rank, int energy_every) {
   bh_rank_opts o;
   bh_rank_default_opts(&o);
   o.split = split;
@@ -64,19 +68,45 @@ static int run_group(int N, int frames, int warmup, bool quiet, const bh_params&
   CK(bh_group_sync(g));
   printf("------------------------------------------\n");
   printf("\n%-10s | %-15s | %-10s\n", "Frame", "Trajanje (ms)", "FPS");  // ref:351
-  double sum = 0.0;
+  double sum = 0.0, sum_plain = 0.0;
+  int energy_frames = 0;
+  bh_energy_stats es;
+  double e0 = 0.0;
+  // an energy step measures the state it starts from: frame 0 gives E0, frame f (a multiple of K) the state after f
+  auto energy_line = [&](int after_frames) {
+    printf("energy step %d K %.9e W %.9e E %.9e dE/|E0| %.3e\n", warmup + after_frames, es.kinetic, es.potential,
+           es.total, e0 != 0.0 ? (es.total - e0) / (e0 < 0.0 ? -e0 : e0) : 0.0);
+  };
   for (int frame = 0; frame < frames; frame++) {
+    const bool measure = energy_every > 0 && frame % energy_every == 0;
     const double t0 = now_ms();
-    CK(bh_step_group(g, 1));
+    if (measure)
+      CK(bh_step_group_energy(g, &es));
+    else
+      CK(bh_step_group(g, 1));
     CK(bh_group_sync(g));  // bh_sync of every rank: BH_ERR_DEVICE_FLAG if a sticky device flag is set anywhere
     const double ms = now_ms() - t0;
     sum += ms;
+    if (measure)
+      energy_frames++;
+    else
+      sum_plain += ms;
     if (!quiet) printf("%-10d | %-15.3f | %-10.1f\n", frame, ms, 1000.0 / ms);  // ref:366
+    if (measure && frame == 0) e0 = es.total;
+    if (measure && frame > 0) energy_line(frame);
   }
-  // the same frames without a host synchronisation per frame (what a caller that only needs the final state pays)
+  // the same frames without a host synchronisation per frame (what a caller that only needs the final state pays);
+  // with --energy its first step measures the state after the last frame when that is a multiple of K
+  const bool last_line = energy_every > 0 && frames > 0 && frames % energy_every == 0;
   const double t0 = now_ms();
-  CK(bh_step_group(g, frames));
+  if (last_line) {
+    CK(bh_step_group_energy(g, &es));
+    CK(bh_step_group(g, frames - 1));
+  } else {
+    CK(bh_step_group(g, frames));
+  }
   CK(bh_group_sync(g));
+  if (last_line) energy_line(frames);
   const double free_run = (now_ms() - t0) / (frames > 0 ? frames : 1);
   const double avg = sum / (frames > 0 ? frames : 1);
   double ph[BH_RANK_PHASES];
@@ -97,6 +127,9 @@ static int run_group(int N, int frames, int warmup, bool quiet, const bh_params&
          "rounds %d LET retries %d\n",
          ph_steps, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], info.n_loc, info.stride, info.mig_last, info.mig_rounds,
          info.let_retries);
+  if (energy_every > 0)
+    printf("energy: %d of %d frames measured the energy; the other %d frames avg %.3f ms/step\n", energy_frames, frames,
+           frames - energy_frames, sum_plain / (frames - energy_frames > 0 ? frames - energy_frames : 1));
   if (replay) {
     // Between X3 and the end of the force on a GPU of its own, rank by rank (the others idle): the last step's force
     // phase run again in every form, an idle wave in the place of X4 (bh_rank_replay_force_phase)
@@ -206,10 +239,6 @@ int main(int argc, char** argv) {
     CK(bh_ic_disc(N, seed, p.G, x.data(), y.data(), z.data(), vx.data(), vy.data(), vz.data(), m.data()));
 
   if (!devs.empty() || gpus > 1 || dist) {
-    if (energy_every > 0) {
-      fprintf(stderr, "--energy needs a single context (bh_energy is not defined for the multi-GPU step)\n");
-      return 2;
-    }
     if (multipole != 1) {
       fprintf(stderr, "--multipole 2 needs a single context (the multi-GPU step has no quadrupole moments)\n");
       return 2;
@@ -218,7 +247,8 @@ int main(int argc, char** argv) {
       for (int q = 0; q < (gpus > 0 ? gpus : 1); q++) devs.push_back(device + q);
     std::vector<float> a[7] = {x, y, z, vx, vy, vz, m};
     return run_group(N, frames, warmup, quiet, p, devs, split, split_pct,
-                     plummer ? "plummer" : (msvc ? "disc(msvc rand)" : "disc"), a, dump_path, snap_path, replay, replay_rank);
+                     plummer ? "plummer" : (msvc ? "disc(msvc rand)" : "disc"), a, dump_path, snap_path, replay, replay_rank,
+                     energy_every);
   }
 
   bh_ctx* c = nullptr;
